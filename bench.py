@@ -128,6 +128,40 @@ def algorithmic_bytes(nq, nv, nu, nobs):
     return 4 * (2 * nq + 2 * nv + nu + nobs + 1) + 2
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(ret):
+    """The arrays a caller of env.step receives, by name (info["critic_state"] is obs_buf itself and is not repeated)."""
+    obs, rew, term, trunc, info = ret
+    out = {"obs": obs, "reward": rew, "terminated": term, "truncated": trunc}
+    out.update((k, v) for k, v in info.items() if k != "critic_state")
+    return out
+
+
+def dump_outputs(dirname, arrays, seed=0):
+    """--dump-outputs: every array as <dirname>/<name>.npy, float64 if it is float64 and float32 otherwise.  Beyond
+    DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of env rows is kept from every array; its row indices are written
+    to sample_rows.npy."""
+    host = {}
+    for k, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[k] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    n = len(next(iter(host.values())))
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(dirname, exist_ok=True)
+    rows_path = os.path.join(dirname, "sample_rows.npy")
+    if total > DUMP_LIMIT_BYTES:
+        keep = max(1, DUMP_LIMIT_BYTES // (total // n + 8))
+        rows = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        host = {k: a[rows] for k, a in host.items()}
+        host["sample_rows"] = rows.astype(np.float64)
+    elif os.path.exists(rows_path):
+        os.remove(rows_path)                                    # left by an earlier, sampled dump into the same directory
+    for k, a in host.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
 def usable_cores():
     """Cores this process may really use: sched affinity capped by the cgroup CPU quota."""
     n = len(os.sched_getaffinity(0))
@@ -140,13 +174,27 @@ def usable_cores():
     return n
 
 
+def native_oracle(O):
+    """O.use_native_build() on a copy of the oracle's sources in a temporary directory: the -O3 -march=native build is made
+    on the box it is timed on, and the checkout it runs from may be read-only.  Returns the build flags."""
+    import atexit
+    import shutil
+    import tempfile
+    tmp = tempfile.mkdtemp(prefix="smplsim_oracle_native_")
+    atexit.register(shutil.rmtree, tmp, True)
+    for f in ("oracle.c", "oracle.h", "Makefile"):
+        shutil.copy2(os.path.join(O._HERE, f), tmp)
+    O._HERE = tmp                                               # the oracle module builds and loads its libraries from here on
+    return O.use_native_build()
+
+
 def cpu_baseline(seconds=12.0):
     """The CPU oracle (float64 C restatement; 'port', NOT MuJoCo — MuJoCo is not installable here) on the
     host cores, same workload shape, bounded sample.  Built here, on the box it is timed on, with -O3 -march=native
     (BASELINE.md §3); the tests use the portable -O2 build."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from oracle import oracle as O
-    flags = O.use_native_build()
+    flags = native_oracle(O)
     from helpers import oracle_model
     cores = usable_cores()
     om = oracle_model()
@@ -305,15 +353,17 @@ def run_imitation(args, rank, local_rank, world, dist, dev):
     for i in range(args.steps):
         a = env.reference_actions()                              # the stand-in policy (one clip lookup launch + two elementwise ones)
         if env.fused:
-            env.step(a, _events=(ev0[i], ev1[i]))                # events around the ONE launch of the step (ss_imitation_step_fused)
+            last = env.step(a, _events=(ev0[i], ev1[i]))         # events around the ONE launch of the step (ss_imitation_step_fused)
         else:
             ev0[i].record()
-            env.step(a)                                          # --unfused: the whole launch sequence
+            last = env.step(a)                                   # --unfused: the whole launch sequence
             ev1[i].record()
         rew_acc.add_(env.rew_buf); end_acc.add_(env.terminated); end_acc.add_(env.truncated)
     rew_sum, ended = rew_acc.mean(), end_acc.sum()
     shard.barrier(dist, world, dev)
     elapsed = shard.max_over_ranks(dist, world, time.perf_counter() - t0, dev)
+    if args.dump_outputs and rank == 0:                          # before the kernel timings below write into the same buffers
+        dump_outputs(args.dump_outputs, step_outputs(last))
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in zip(ev0, ev1)]))
     # the row's own kernels, timed alone on this stream: imitation step (per launch) and the three cooking launches
     reps = 200
@@ -439,7 +489,12 @@ def main(argv=None):
     ap.add_argument("--workload", default="smpl", choices=["smpl", "getup", "smplx", "imitation"],
                     help="smpl = BASELINE config 2 (the metric); getup = config 3 shard (Fall init, getup task); smplx = config 4; "
                          "imitation = config 5 shard (motion clips, tracking reward)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (obs, reward, flags, final observations; rank 0) "
+                         "as DIR/<name>.npy in float32 / float64, at most 64 MB in all (a fixed, seeded sample of env rows beyond that)")
     args = ap.parse_args(argv)
+    if args.dump_outputs and args.steps < 1:
+        raise SystemExit("--dump-outputs needs at least one timed step (--steps >= 1)")
 
     import torch
     from smplsim_amd import shard
@@ -495,10 +550,12 @@ def main(argv=None):
     t0 = time.perf_counter()
     for i in range(args.steps):
         # env.step = LPT hand-out order (argsort of last step's Newton counts) + the fused step launch + masked autoreset
-        env.step(abuf.uniform_(-1.0, 1.0, generator=g), _events=(ev0[i], ev1[i]))
+        last = env.step(abuf.uniform_(-1.0, 1.0, generator=g), _events=(ev0[i], ev1[i]))
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed = shard.max_over_ranks(dist, world, elapsed, dev)
+    if args.dump_outputs and rank == 0:                          # before the parity probe below steps this env once more
+        dump_outputs(args.dump_outputs, step_outputs(last))
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in zip(ev0, ev1)]))
     finite = bool(torch.isfinite(env.obs_buf).all().item())
     nwarn = int(env.nwarn.sum().item())

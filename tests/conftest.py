@@ -3,8 +3,7 @@ import sys
 
 import pytest
 
-# Some tests load modules from the read-only reference checkout (/root/reference): never leave __pycache__/*.pyc in it.  Set before
-# any such import and inherited by the forked sampler workers of tests/test_reference_agent.py.
+# No __pycache__/*.pyc from a test run: set before any import and inherited by the subprocesses the tests start.
 sys.dont_write_bytecode = True
 os.environ.setdefault("PYTHONDONTWRITEBYTECODE", "1")
 
@@ -14,22 +13,18 @@ if ROOT not in sys.path:
 
 
 def pytest_configure(config):
-    config.addinivalue_line("markers", "gpu: needs a real MI355X (run on the GPU box via gpurun)")
-    config.addinivalue_line("markers", "refonly: needs /root/reference (build container only)")
+    config.addinivalue_line("markers", "gpu: needs a real MI355X")
 
 
 def pytest_collection_modifyitems(config, items):
-    have_ref = os.path.isdir("/root/reference/smpl_sim")
     have_gpu = None
     for it in items:
-        if "refonly" in it.keywords and not have_ref:
-            it.add_marker(pytest.mark.skip(reason="/root/reference not present"))
         if "gpu" in it.keywords:
             if have_gpu is None:
                 import torch
                 have_gpu = torch.cuda.is_available()
             if not have_gpu:                                 # a plain `pytest tests` in the GPU-less container stays green
-                it.add_marker(pytest.mark.skip(reason="no ROCm GPU in this environment (run on the MI355X box via gpurun)"))
+                it.add_marker(pytest.mark.skip(reason="no ROCm GPU in this environment"))
 
 
 @pytest.fixture()

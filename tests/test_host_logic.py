@@ -91,18 +91,32 @@ def test_shard_ranges_partition_the_batch():
     assert shard_seed(1234, 3) == 1237
 
 
-def test_import_shim_lets_the_rest_of_the_reference_resolve_behind_it():
-    """With this repo before a SMPLSim checkout on sys.path, smpl_sim.envs is ours and smpl_sim.learning is the reference's."""
-    ref = "/root/reference"
-    if not os.path.isdir(os.path.join(ref, "smpl_sim", "learning")):
-        pytest.skip("no reference checkout in this environment")
-    code = ("import smpl_sim.envs.tasks as t, smpl_sim.learning.mlp as m, smpl_sim.smpllib.motion_lib_smpl as ml, sys;"
-            "print(t.HumanoidEnv.__module__, m.__file__, ml.MotionLibSMPL.__module__)")
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + ref, PYTHONDONTWRITEBYTECODE="1")
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd="/tmp")
+def test_import_shim_lets_the_rest_of_the_reference_resolve_behind_it(tmp_path):
+    """With this repo before a SMPLSim checkout on sys.path, smpl_sim.envs is ours and smpl_sim.learning is the checkout's.  The
+    checkout is a stand-in with the reference's package layout: modules the shim must shadow are decoys, the others are found behind it."""
+    ref = tmp_path / "checkout"
+    files = {
+        "smpl_sim/__init__.py": "raise ImportError('the checkout package body must not run: the shim comes first')\n",
+        "smpl_sim/envs/__init__.py": "",
+        "smpl_sim/envs/tasks/__init__.py": "class HumanoidEnv: pass\n",                      # decoy
+        "smpl_sim/learning/__init__.py": "",
+        "smpl_sim/learning/mlp.py": "class MLP: pass\n",
+        "smpl_sim/smpllib/__init__.py": "",
+        "smpl_sim/smpllib/motion_lib_smpl.py": "class MotionLibSMPL: pass\n",               # decoy
+        "smpl_sim/smpllib/smpl_joint_names.py": "SMPL_BONE_ORDER_NAMES = []\n",
+    }
+    for name, text in files.items():
+        (ref / name).parent.mkdir(parents=True, exist_ok=True)
+        (ref / name).write_text(text)
+    code = ("import smpl_sim.envs.tasks as t, smpl_sim.learning.mlp as m, smpl_sim.smpllib.motion_lib_smpl as ml, "
+            "smpl_sim.smpllib.smpl_joint_names as jn, sys;"
+            "print(t.HumanoidEnv.__module__, m.__file__, ml.MotionLibSMPL.__module__, jn.__file__)")
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + str(ref), PYTHONDONTWRITEBYTECODE="1")
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd=tmp_path)
     assert out.returncode == 0, out.stderr[-2000:]
-    mod, mlp_file, ml_mod = out.stdout.split()
-    assert mod.startswith("smplsim_amd.") and mlp_file.startswith(ref) and ml_mod == "smplsim_amd.motion_lib"
+    mod, mlp_file, ml_mod, jn_file = out.stdout.split()
+    assert mod.startswith("smplsim_amd.") and mlp_file.startswith(str(ref)) and ml_mod == "smplsim_amd.motion_lib"
+    assert jn_file.startswith(str(ref))
 
 
 def test_mlp_entry_points_validate_their_arguments():

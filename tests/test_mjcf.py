@@ -1,11 +1,13 @@
 """Model compiler: known answers from SURVEY.md §7/§8c and agreement with the oracle's
 independent compile (XML -> primitives in oracle.py -> mass/inertia/invweight0 in C)."""
 import dataclasses
+import gzip
+import os
 
 import numpy as np
 import pytest
 
-from helpers import model_const, oracle_model
+from helpers import GOLDEN, model_const, oracle_model
 from oracle import oracle as O
 from smplsim_amd.mjcf import MjcfError, compile_mjcf
 from smplsim_amd.mjcf_writer import default_xml_str
@@ -69,11 +71,13 @@ def test_rejects_unsupported_models():
         compile_mjcf("not xml")
 
 
-@pytest.mark.refonly
 @pytest.mark.parametrize("ref,name", [("smpl_sim/data/assets/mjcf/smpl_humanoid.xml", "smpl_humanoid"),
                                       ("smpl_humanoid.xml", "smplx_humanoid")])
 def test_shipped_table_equals_reference_xml(ref, name):
-    a = compile_mjcf(open("/root/reference/" + ref).read())
+    """The reference's two MJCF files (ref = the path in the reference tree), stored gzipped under tests/golden/mjcf at the same
+    relative path, compile to the packaged tables."""
+    with gzip.open(os.path.join(GOLDEN, "mjcf", ref + ".gz"), "rt") as f:
+        a = compile_mjcf(f.read())
     b = model_const(name)
     for f in dataclasses.fields(a):
         x, y = getattr(a, f.name), getattr(b, f.name)

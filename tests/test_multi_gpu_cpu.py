@@ -122,6 +122,43 @@ def test_bench_main_strong_scaling_switch(tmp_path):
     assert "1.25x" in res["config"]["scaling_note"] and "--envs-total" in res["config"]["scaling_note"]
 
 
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(tmp_path):
+    """--dump-outputs DIR: what env.step returned in the last timed step, one float32 .npy per array; the same arguments give the
+    same files, one more timed step gives other ones (--steps is the number of timed steps)."""
+    def run(name, steps):
+        d = tmp_path / name
+        res = _run_world(tmp_path, _BENCH, ["--gpus", "1", "--envs-per-gpu", "3", "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline",
+                                            "--no-reference-contact-set", "--dump-outputs", str(d)], world=1)
+        assert res["steps"] == steps
+        return {f.stem: np.load(f) for f in sorted(d.glob("*.npy"))}
+    a, b, c = run("a", 2), run("b", 2), run("c", 3)
+    assert sorted(a) == ["final_observation", "obs", "reward", "terminated", "truncated"]
+    assert a["obs"].shape == (3, 289) and a["final_observation"].shape == (3, 289) and a["reward"].shape == (3,)
+    assert all(v.dtype == np.float32 for v in a.values()) and np.isfinite(a["obs"]).all()
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert not np.array_equal(a["obs"], c["obs"])
+
+
+def test_bench_dump_outputs_sample_rows_beyond_the_limit(tmp_path, monkeypatch):
+    """Past the size limit every array keeps the same fixed, seeded sample of rows, and the row indices are written beside them."""
+    import torch
+    import bench
+    x = torch.arange(1000 * 8, dtype=torch.float32).reshape(1000, 8)
+    flags = torch.arange(1000) % 3 == 0
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4000)
+    bench.dump_outputs(str(tmp_path / "a"), {"obs": x, "terminated": flags})
+    bench.dump_outputs(str(tmp_path / "b"), {"obs": x, "terminated": flags})
+    got = {f.name: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    rows = got["sample_rows.npy"]
+    assert rows.dtype == np.float64 and sum(v.nbytes for v in got.values()) <= 4000
+    assert np.array_equal(got["obs.npy"], x.numpy()[rows.astype(int)])
+    assert np.array_equal(got["terminated.npy"], flags.numpy()[rows.astype(int)].astype(np.float32))
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "sample_rows.npy"))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 << 20)
+    bench.dump_outputs(str(tmp_path / "a"), {"obs": x})      # under the limit: whole arrays, and no stale sample index
+    assert not (tmp_path / "a" / "sample_rows.npy").exists() and np.load(tmp_path / "a" / "obs.npy").shape == (1000, 8)
+
+
 def _run_plain(tmp_path, args, extra_env=None, timeout=900):
     """`python worker.py --gpus N ...` with NO rank variables in the environment and no process fan-out on the test's side: the ranks
     are whatever bench.main starts by itself."""
