@@ -66,6 +66,12 @@ int ss_wgrad_bf16(const void *dz, const void *h, float *dw, int32_t Mb, int32_t 
 int ss_gaussian_sample(const float *mean, const float *noise, const float *log_std, int32_t M, int32_t dim, float *action, int32_t lda,
                        float *action_env, int32_t lde, float clip_lo, float clip_hi, float *logp, void *stream);
 
+/* Test hook: the GEMM instantiation launched last by an ss_linear_* / ss_wgrad_bf16 call on the calling host thread, as
+ * "<family> mode=<G256 mode or -> bn=<BN> bk=<BK> waves=<waves per workgroup> out=<bf16|f32|f32acc> ksplit=<K shares> kper=<K tiles per share>"
+ * with family linear / glds / train / gemm256 / wgrad (empty before the first launch).  Copies it, NUL-terminated and truncated to len - 1
+ * characters, into buf; returns its full length. */
+int ss_debug_last_gemm(char *buf, int32_t len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@
 // the products to pair up; the C layout is col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 #include <string>
@@ -860,6 +861,14 @@ __global__ void __launch_bounds__(256) ss_gaussian_sample_kernel(const float *me
 
 int fail(int code, const char *msg) { ss::last_error() = msg; return code; }
 
+// ss_debug_last_gemm: which instantiation the host dispatch launched last on this thread (written at every launch site; tests assert it)
+thread_local std::string last_gemm;
+void note_gemm(const char *family, int bn, int bk, int waves, const char *out, const char *mode, int ksplit, int kper) {
+  char b[160];
+  snprintf(b, sizeof b, "%s mode=%s bn=%d bk=%d waves=%d out=%s ksplit=%d kper=%d", family, mode, bn, bk, waves, out, ksplit, kper);
+  last_gemm = b;
+}
+
 }  // namespace
 
 extern "C" {
@@ -881,6 +890,7 @@ int ss_linear_bf16(const void *x, const void *w, const float *bias, void *y, int
       auto kern_ = ss_gemm256_kernel<G256_PLAIN>;
       const size_t epi_ = (size_t)gemm256::TILE * (gemm256::TILE + 8) * sizeof(__bf16);
       if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize, (int)epi_) != hipSuccess) return fail(SS_ERR_HIP, "cannot size the GEMM's LDS");
+      note_gemm("gemm256", 256, 64, 8, "bf16", "PLAIN", 1, 0);
       hipLaunchKernelGGL(kern_, dim3((N + 255) / 256, (M + 255) / 256, 1), dim3(512), epi_, st, a);
       hipError_t e = hipGetLastError();
       return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
@@ -919,12 +929,14 @@ int ss_linear_bf16(const void *x, const void *w, const float *bias, void *y, int
       auto kern_ = ss_linear_glds_kernel<BN_, F32_>;                                                                           \
       const size_t l3_ = (size_t)3 * (BM + BN_) * 64 * sizeof(__bf16);                                                         \
       if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3_) != hipSuccess) return fail(SS_ERR_HIP, "cannot size the GEMM's LDS"); \
+      note_gemm("glds", BN_, 64, 8, F32_ ? "f32" : "bf16", "-", 1, 0);                                                      \
       hipLaunchKernelGGL(kern_, grid, dim3(512), l3_, st, X, Wt, bias, y, M, N, K, ldy, act, remap);                            \
     } else if (waves8 && BK_ == 64) {                                                                                          \
       auto kern_ = ss_linear_kernel<BN_, BK_, F32_, 4>;                                                                        \
       /* per launch: the attribute belongs to the (kernel, device) pair and the call is a table write (a process-wide flag left */ \
       /* the wide tiles of a second GPU at the 64 KB default: ADVICE r4) */                                                     \
       if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_) != hipSuccess) return fail(SS_ERR_HIP, "cannot size the GEMM's LDS"); \
+      note_gemm("linear", BN_, BK_, 8, F32_ ? "f32" : "bf16", "-", 1, 0);                                                   \
       hipLaunchKernelGGL(kern_, grid, dim3(512), lds_, st, X, Wt, bias, y, M, N, K, ldy, act, remap);                           \
     } else {                                                                                                                   \
       auto kern_ = ss_linear_kernel<(BN_ > 128 ? 128 : BN_), BK_, F32_, 2>;                                                     \
@@ -932,6 +944,7 @@ int ss_linear_bf16(const void *x, const void *w, const float *bias, void *y, int
           hipFuncSetAttribute(reinterpret_cast<const void *>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize,                \
                               (int)((size_t)2 * (BM + (BN_ > 128 ? 128 : BN_)) * (BK_ + 8) * sizeof(__bf16))) != hipSuccess) return fail(SS_ERR_HIP, "cannot size the GEMM's LDS"); \
       const size_t l4a_ = (size_t)2 * (BM + (BN_ > 128 ? 128 : BN_)) * (BK_ + 8) * sizeof(__bf16), l4b_ = (size_t)BM * ((BN_ > 128 ? 128 : BN_) + 8) * sizeof(__bf16); \
+      note_gemm("linear", BN_ > 128 ? 128 : BN_, BK_, 4, F32_ ? "f32" : "bf16", "-", 1, 0);                                 \
       hipLaunchKernelGGL(kern_, dim3((N + (BN_ > 128 ? 128 : BN_) - 1) / (BN_ > 128 ? 128 : BN_), gm), dim3(256),              \
                          l4a_ > l4b_ ? l4a_ : l4b_, st, X, Wt, bias, y, M, N, K, ldy, act, remap);                              \
     }                                                                                                                          \
@@ -1032,6 +1045,7 @@ static int linear_train_impl(const void *x, const void *w, const float *bias, co
     do {                                                                                                                       \
       auto kern_ = ss_gemm256_kernel<MODE_>;                                                                                   \
       if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_)) != hipSuccess) return fail(SS_ERR_HIP, "cannot size the GEMM's LDS"); \
+      note_gemm("gemm256", 256, 64, 8, MODE_ == G256_ACCUM ? "f32acc" : "bf16", &#MODE_[5], a.ksplit, a.kper);                \
       hipLaunchKernelGGL(kern_, grid, dim3(512), LDS_, st, a);                                                                 \
     } while (0)
     if (y_is_f32_accumulate) SS_G256(G256_ACCUM, loop_);
@@ -1053,10 +1067,12 @@ static int linear_train_impl(const void *x, const void *w, const float *bias, co
     if (y_is_f32_accumulate) {                                                                                                 \
       auto kern_ = ss_linear_train_kernel<BN_, true>;                                                                          \
       if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize, (int)loop_) != hipSuccess) return fail(SS_ERR_HIP, "cannot size the GEMM's LDS"); \
+      note_gemm("train", BN_, 64, 8, "f32acc", "-", ksplit, (K / 64 + ksplit - 1) / ksplit);                                \
       hipLaunchKernelGGL(kern_, grid, dim3(512), loop_, st, a);                                                                \
     } else {                                                                                                                   \
       auto kern_ = ss_linear_train_kernel<BN_, false>;                                                                         \
       if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_) != hipSuccess) return fail(SS_ERR_HIP, "cannot size the GEMM's LDS"); \
+      note_gemm("train", BN_, 64, 8, "bf16", "-", 1, 0);                                                                    \
       hipLaunchKernelGGL(kern_, grid, dim3(512), lds_, st, a);                                                                 \
     }                                                                                                                          \
   } while (0)
@@ -1095,9 +1111,16 @@ int ss_wgrad_bf16(const void *dz, const void *h, float *dw, int32_t Mb, int32_t 
   WgradArgs a{static_cast<const __bf16 *>(dz), static_cast<const __bf16 *>(h), dw, n_out, n_in, ldz, ldh, ldw, nkt, per};
   const size_t lds = gemm256::LoopTN::LDS_BYTES;
   if (hipFuncSetAttribute(reinterpret_cast<const void *>(ss_wgrad_tn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return fail(SS_ERR_HIP, "cannot size the GEMM's LDS");
+  note_gemm("wgrad", 256, 64, 8, "f32acc", "-", ks, per);
   hipLaunchKernelGGL(ss_wgrad_tn_kernel, dim3(gx, gy, ks), dim3(512), lds, (hipStream_t)stream, a);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
+}
+
+int ss_debug_last_gemm(char *buf, int32_t len) {
+  if (!buf || len < 1) return fail(SS_ERR_INVALID, "null argument");
+  snprintf(buf, (size_t)len, "%s", last_gemm.c_str());
+  return (int)last_gemm.size();
 }
 
 int ss_gaussian_sample(const float *mean, const float *noise, const float *log_std, int32_t M, int32_t dim, float *action, int32_t lda,

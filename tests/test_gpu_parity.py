@@ -1088,11 +1088,21 @@ def test_linear_bf16_train_kernel_outputs(M, N, K, act):
     assert lib().ss_linear_bf16_train(ptr(x), ptr(w), ptr(b), None, ptr(y), None, None, M, N, K - 32, N, 0, 0, 0, st) == -1   # K: multiples of 64
 
 
+def _last_gemm():
+    import ctypes as C
+    from smplsim_amd._lib import lib
+    buf = C.create_string_buffer(256)
+    assert lib().ss_debug_last_gemm(buf, 256) >= 0
+    return buf.value.decode()
+
+
 @pytest.mark.parametrize("M,N,K,act", [(2048, 1536, 2048, "silu"), (300, 260, 128, "tanh"), (4096, 512, 1024, "none"), (1000, 1000, 384, "relu")])
 def test_gemm256_kernel_outputs(M, N, K, act, monkeypatch):
     """The 256 x 256 macro-tile kernel behind ss_linear_bf16_train (csrc/ss_gemm256.h: staggered wave rows, copies in flight across barriers):
     the same three outputs against torch on asymmetric bf16 operands, ragged M and N, the shortest K loop it takes (two K tiles), and the same
-    bits from every one of 20 launches (a copy that lands after its reader shows up as a launch that differs)."""
+    bits from every one of 20 launches (a copy that lands after its reader shows up as a launch that differs).  Without the multiplying operand
+    the forward mode (y, y^T, act'); with it the dX mode (y, y^T); y, y^T and act' WITH the operand is not a mode of the 256 x 256 kernel and
+    falls back to the 128-row kernel (checked against the same reference)."""
     import ctypes as C
     from smplsim_amd import _cabi
     from smplsim_amd._lib import lib
@@ -1106,7 +1116,7 @@ def test_gemm256_kernel_outputs(M, N, K, act, monkeypatch):
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     fn = {"silu": torch.nn.functional.silu, "tanh": torch.tanh, "relu": torch.relu, "none": lambda t: t}[act]
     ldt = (M + 7) // 8 * 8
-    for use_mul in (False, True):
+    for use_mul, use_d, mode in ((False, True, "FWD"), (True, False, "DX"), (True, True, None)):
         z = x.float() @ w.float().T + b
         if use_mul:
             z = z * mul.float()
@@ -1116,18 +1126,21 @@ def test_gemm256_kernel_outputs(M, N, K, act, monkeypatch):
         first = None
         for rep in range(20):
             y = torch.zeros(M, N, dtype=torch.bfloat16, device="cuda"); yt = torch.zeros(N, ldt, dtype=torch.bfloat16, device="cuda")
-            d = torch.zeros(M, N, dtype=torch.bfloat16, device="cuda")
+            d = torch.zeros(M, N, dtype=torch.bfloat16, device="cuda") if use_d else None
             assert lib().ss_linear_bf16_train(ptr(x), ptr(w), ptr(b), ptr(mul if use_mul else None), ptr(y), ptr(yt), ptr(d), M, N, K, N, ldt,
                                               _cabi.ACTIVATIONS[act], 0, st) == 0
+            kern = _last_gemm()
+            assert kern.startswith(f"gemm256 mode={mode} ") if mode else kern.startswith("train "), (use_mul, use_d, kern)
             torch.cuda.synchronize()
             if first is None:
-                first = (y.clone(), yt.clone(), d.clone())
+                first = (y.clone(), yt.clone(), d.clone() if use_d else None)
                 tol = 1e-2 * max(1.0, ref.abs().max().item())
                 assert (y.float() - ref.detach()).abs().max().item() < tol
                 assert torch.equal(yt[:, :M], y.t())
-                assert (d.float() - dref).abs().max().item() < 2e-2
+                if use_d:
+                    assert (d.float() - dref).abs().max().item() < 2e-2
             else:
-                assert torch.equal(y, first[0]) and torch.equal(yt, first[1]) and torch.equal(d, first[2]), rep
+                assert torch.equal(y, first[0]) and torch.equal(yt, first[1]) and (not use_d or torch.equal(d, first[2])), rep
     # the accumulating form: K split into shares of an even number of tiles, against the fp32 product
     yf = torch.zeros(M, N + 3, device="cuda")
     assert lib().ss_linear_bf16_train(ptr(x), ptr(w), None, None, ptr(yf), None, None, M, N, K, N + 3, 0, 0, 1, st) == 0
