@@ -17,8 +17,8 @@
 // the products to pair up; the C layout is col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 #include <string>
 
@@ -606,14 +606,6 @@ __global__ void __launch_bounds__(512) ss_gemm256_kernel(const LinearTrainArgs a
   gemm256::Loop L;
   L.init(a.X, a.W, M, N, K, m0, n0, kt0, reinterpret_cast<char *>(lds_g));
   L.run(acc, nkt);
-#ifdef SS_GEMM256_ABLATE
-  if (a.xcd_remap & 2) {                                      // K loop only: one store per lane keeps the accumulators alive
-    float sacc = 0.f;
-    for (int i = 0; i < 4; i++) for (int j = 0; j < 2; j++) for (int r = 0; r < 16; r++) sacc += acc[i][j][r];
-    if (sacc == 12345.f) reinterpret_cast<__bf16 *>(a.Y)[threadIdx.x] = (__bf16)sacc;
-    return;
-  }
-#endif
   const int tid = threadIdx.x, lane = L.lane, wr = L.wr, wc = L.wc;
   const int col_l = wc * 64 + (lane & 31), row_l = wr * 128 + 4 * (lane >> 5);   // + tn * 32 resp. + tm * 32 + (r & 3) + 8 * (r >> 2)
   if constexpr (MODE == G256_ACCUM) {
@@ -717,9 +709,6 @@ __global__ void __launch_bounds__(512) ss_gemm256_kernel(const LinearTrainArgs a
       for (int i = 0; i < 8; i++) {
         const int id = tid + 512 * i, lr = id / CPR, cc = (id % CPR) * 8, row = m0 + (lr >> 6) * 128 + half * 64 + (lr & 63), col = n0 + cc;
         if (row >= M || col >= N) continue;
-#ifdef SS_GEMM256_ABLATE
-        if ((a.xcd_remap & 4) && v[i][0] != 0x12345678u) continue;
-#endif
         if (rows_vec && col + 8 <= N) *reinterpret_cast<u32x4 *>(dst + (size_t)row * a.ldy + col) = v[i];
         else store_chunk_edge(dst + (size_t)row * a.ldy + col, v[i], N - col);
       }
@@ -861,12 +850,141 @@ __global__ void __launch_bounds__(256) ss_gaussian_sample_kernel(const float *me
 
 int fail(int code, const char *msg) { ss::last_error() = msg; return code; }
 
-// ss_debug_last_gemm: which instantiation the host dispatch launched last on this thread (written at every launch site; tests assert it)
+// ---- host dispatch: every GEMM launch is planned from the entry point's arguments alone, one function per decision, and launched by
+// launch_gemm, which knows exactly the instantiations these plans can name
+enum GemmFamily { GEMM_GLDS, GEMM_LINEAR, GEMM_TRAIN, GEMM_256, GEMM_WGRAD };
+struct GemmPlan {
+  GemmFamily family;
+  bool f32;                           // fp32 output (GEMM_GLDS, GEMM_LINEAR) or fp32 partial sums added by atomics (the others)
+  int mode = -1;                      // GEMM_256: G256_*
+  int bn = 256, bk = 64, waves = 8;   // tile width, K tile, waves per workgroup (64 * waves threads)
+  dim3 grid;
+  size_t lds = 0;                     // dynamic LDS bytes
+  int ksplit = 1, kper = 0;           // K shares over grid.z and 64-wide K tiles per share (the accumulating forms)
+};
+
+// Tile width of the 128-row kernels: the one whose tile count fills the chip's 256 CUs in whole rounds (4096 x 2048 -> 256 columns, x 1536 ->
+// 192, x 1024 -> 128, x 512 -> 64: exactly one 128-row tile per CU each; round 3 used 128 x 128 for the two widest layers = 1.5 rounds of
+// workgroups, a third of the chip idle in the second), ties to the wider tile (more MFMAs per LDS byte and per barrier).  Widths above 128
+// only when `wide`, above 64 only up to N.  `whole`: every round counts as full, only the columns wasted by the last tile count (the
+// accumulating form fills the chip with its K split, and so does a batch of thousands of rows: there the widest tile wins on every product
+// measured, profiles/r06_train_gemm_sweep.txt).
+int fill_bn(int M, int N, bool wide, bool whole) {
+  const int gm = (M + BM - 1) / BM;
+  int bn = 64;
+  double best = -1;
+  for (const int c : {256, 192, 128, 64}) {
+    if ((c > 128 && !wide) || (c > 64 && N < c)) continue;
+    const long long tiles = (long long)((N + c - 1) / c) * gm, rounds = (tiles + 255) / 256;
+    const double fill = (whole ? 1.0 : (double)tiles / (double)(rounds * 256)) * ((double)N / (double)(((N + c - 1) / c) * c));
+    if (fill > best + 1e-9) { best = fill; bn = c; }
+  }
+  return bn;
+}
+
+// what the 256 x 256 kernel (ss_gemm256.h) takes besides its row and output counts: whole pairs of K tiles, 32-bit source offsets
+bool fits_256(int M, int N, int K) { return K >= 128 && K % 128 == 0 && (long long)M * K < (1ll << 32) && (long long)N * K < (1ll << 32); }
+
+// K split of the 256 x 256 kernels' accumulating forms: as many shares as fill ONE round of the 256 CUs (one workgroup per CU; 28 tiles x
+// 19 shares = 532 workgroups ran as three rounds), at least 8 K tiles each, then shares of an even number of K tiles (nkt is even: the last too)
+void split_256(GemmPlan &p, long long tiles, int nkt) {
+  p.ksplit = std::max(1, std::min((int)(256 / tiles), nkt / 8));
+  p.kper = (nkt + p.ksplit - 1) / p.ksplit;
+  p.kper += p.kper & 1;
+  p.ksplit = (nkt + p.kper - 1) / p.kper;
+}
+
+GemmPlan plan_256(int M, int N, int K, int mode) {
+  constexpr int T = gemm256::TILE;
+  GemmPlan p{GEMM_256, mode == G256_ACCUM, mode};
+  const int gx = (N + T - 1) / T, gy = (M + T - 1) / T;
+  if (p.f32) split_256(p, (long long)gx * gy, K / 64);
+  p.grid = dim3(gx, gy, p.ksplit);
+  p.lds = p.f32 ? gemm256::LOOP_LDS_BYTES : (size_t)T * (T + 8) * sizeof(__bf16);
+  return p;
+}
+
+// ss_linear_bf16.  Thousands of rows (the update's and GAE's passes over the whole rollout): the 256 x 256 kernel, 1.19 PFLOP/s on 53 248 x 1536
+// x 2048 against 0.60 for the 128-row tiles; at the sampler's 4096 rows it has at most 128 tiles for 256 CUs and stays out.  The wide tiles need
+// the K tile of 64 and a deep K (289 -> 2048 has 5 K tiles: the 256-column tile's longer prologue / epilogue made it 24 vs 18 us).
+GemmPlan plan_linear(int M, int N, int K, bool f32) {
+  if (!f32 && (long long)((M + 255) / 256) * ((N + 255) / 256) >= 230 && N % 256 == 0 && K >= 256 && fits_256(M, N, K)) return plan_256(M, N, K, G256_PLAIN);
+  // round 5: asynchronous global -> LDS copies, three K tiles in flight.  A shallow K keeps the two-stage kernel (two workgroups per CU hide
+  // its short loop better): 8 waves of 32 x BN/2 each, twice the waves per SIMD; K an odd multiple of 32: 4 waves with K tiles of 32
+  const bool k64 = K % 64 == 0, glds = k64 && K >= 512;
+  GemmPlan p{glds ? GEMM_GLDS : GEMM_LINEAR, f32};
+  p.bn = fill_bn(M, N, glds, false);
+  p.bk = k64 ? 64 : 32;
+  p.waves = k64 ? 8 : 4;
+  p.grid = dim3((N + p.bn - 1) / p.bn, (M + BM - 1) / BM);
+  // the two-stage kernel: the K loop's two stages; the epilogue stages the output tile in the same memory
+  p.lds = glds ? (size_t)3 * (BM + p.bn) * 64 * sizeof(__bf16) : std::max((size_t)2 * (BM + p.bn) * (p.bk + 8), (size_t)BM * (p.bn + 8)) * sizeof(__bf16);
+  return p;
+}
+
+// ss_linear_bf16_train's 128-row kernel: the tile width as above, then the K split of the accumulating form: products whose output has fewer
+// tiles than CUs and a deep contraction (the weight gradients: K = the batch) are cut along K into as many shares as fill about two rounds
+GemmPlan plan_train(int M, int N, int K, bool acc) {
+  const int gm = (M + BM - 1) / BM, nkt = K / 64;
+  GemmPlan p{GEMM_TRAIN, acc};
+  p.bn = fill_bn(M, N, K >= 512, acc || gm >= 64);
+  if (acc) {
+    const long long tiles = (long long)((N + p.bn - 1) / p.bn) * gm;
+    p.ksplit = std::max(1, std::min((int)((512 + tiles - 1) / tiles), nkt / 8));   // at least 8 K tiles per share
+    p.kper = (nkt + p.ksplit - 1) / p.ksplit;
+  }
+  p.grid = dim3((N + p.bn - 1) / p.bn, gm, p.ksplit);
+  const size_t loop = (size_t)3 * (BM + p.bn) * 64 * sizeof(__bf16), epi = (size_t)std::max(BM * (p.bn + 8), p.bn * (BM + 8)) * sizeof(__bf16);
+  p.lds = acc ? loop : std::max(loop, epi);
+  return p;
+}
+
+// the kernel of a plan: exactly the instantiations the plans above can name
+const void *gemm_kernel(const GemmPlan &p) {
+  typedef const void *F;
+  const int w = p.bn / 64 - 1, o = p.f32;   // BN 64 / 128 / 192 / 256
+  switch (p.family) {
+  case GEMM_GLDS: {
+    static const F k[4][2] = {{F(ss_linear_glds_kernel<64, false>), F(ss_linear_glds_kernel<64, true>)}, {F(ss_linear_glds_kernel<128, false>), F(ss_linear_glds_kernel<128, true>)},
+                              {F(ss_linear_glds_kernel<192, false>), F(ss_linear_glds_kernel<192, true>)}, {F(ss_linear_glds_kernel<256, false>), F(ss_linear_glds_kernel<256, true>)}};
+    return k[w][o];
+  }
+  case GEMM_LINEAR: {   // BN 64 / 128: 8 waves (4 x 2) with K tiles of 64, 4 waves (2 x 2) with K tiles of 32
+    static const F k[2][2][2] = {{{F(ss_linear_kernel<64, 64, false, 4>), F(ss_linear_kernel<64, 64, true, 4>)}, {F(ss_linear_kernel<128, 64, false, 4>), F(ss_linear_kernel<128, 64, true, 4>)}},
+                                 {{F(ss_linear_kernel<64, 32, false, 2>), F(ss_linear_kernel<64, 32, true, 2>)}, {F(ss_linear_kernel<128, 32, false, 2>), F(ss_linear_kernel<128, 32, true, 2>)}}};
+    return k[p.bk == 32][w][o];
+  }
+  case GEMM_TRAIN: {
+    static const F k[4][2] = {{F(ss_linear_train_kernel<64, false>), F(ss_linear_train_kernel<64, true>)}, {F(ss_linear_train_kernel<128, false>), F(ss_linear_train_kernel<128, true>)},
+                              {F(ss_linear_train_kernel<192, false>), F(ss_linear_train_kernel<192, true>)}, {F(ss_linear_train_kernel<256, false>), F(ss_linear_train_kernel<256, true>)}};
+    return k[w][o];
+  }
+  case GEMM_256: {
+    static const F k[6] = {F(ss_gemm256_kernel<G256_ACCUM>), F(ss_gemm256_kernel<G256_PLAIN>), F(ss_gemm256_kernel<G256_FWD>), F(ss_gemm256_kernel<G256_DX>),
+                           F(ss_gemm256_kernel<G256_FWDN>), F(ss_gemm256_kernel<G256_DXN>)};
+    return k[p.mode];
+  }
+  case GEMM_WGRAD: return F(ss_wgrad_tn_kernel);
+  }
+  return nullptr;
+}
+
+// ss_debug_last_gemm: which instantiation the host dispatch launched last on this thread (tests assert it)
 thread_local std::string last_gemm;
-void note_gemm(const char *family, int bn, int bk, int waves, const char *out, const char *mode, int ksplit, int kper) {
+
+int launch_gemm(const GemmPlan &p, void **args, hipStream_t st) {
+  const void *kern = gemm_kernel(p);
+  // per launch: the attribute belongs to the (kernel, device) pair and the call is a table write (a process-wide flag left
+  // the wide tiles of a second GPU at the 64 KB default: ADVICE r4)
+  if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds) != hipSuccess) return fail(SS_ERR_HIP, "cannot size the GEMM's LDS");
+  static const char *const family[] = {"glds", "linear", "train", "gemm256", "wgrad"}, *const mode[] = {"ACCUM", "PLAIN", "FWD", "DX", "FWDN", "DXN"};
   char b[160];
-  snprintf(b, sizeof b, "%s mode=%s bn=%d bk=%d waves=%d out=%s ksplit=%d kper=%d", family, mode, bn, bk, waves, out, ksplit, kper);
+  snprintf(b, sizeof b, "%s mode=%s bn=%d bk=%d waves=%d out=%s ksplit=%d kper=%d", family[p.family], p.family == GEMM_256 ? mode[p.mode] : "-", p.bn, p.bk,
+           p.waves, !p.f32 ? "bf16" : p.family <= GEMM_LINEAR ? "f32" : "f32acc", p.ksplit, p.kper);
   last_gemm = b;
+  (void)hipLaunchKernel(kern, p.grid, dim3(64 * p.waves), args, p.lds, st);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
 }
 
 }  // namespace
@@ -879,89 +997,15 @@ int ss_linear_bf16(const void *x, const void *w, const float *bias, void *y, int
   if (M < 1 || N < 1 || K < 32 || K % 32 || ldy < N) return fail(SS_ERR_INVALID, "ss_linear_bf16: K must be a positive multiple of 32, ldy >= N");
   if (act < SS_ACT_NONE || act > SS_ACT_RELU) return fail(SS_ERR_INVALID, "unknown activation");
   const __bf16 *X = static_cast<const __bf16 *>(x), *Wt = static_cast<const __bf16 *>(w);
-  hipStream_t st = (hipStream_t)stream;
-  // thousands of rows (the update's and GAE's passes over the whole rollout): the 256 x 256 kernel (ss_gemm256.h), 1.19 PFLOP/s on 53 248 x 1536 x 2048
-  // against 0.60 for the 128-row tiles below; at the sampler's 4096 rows it has at most 128 tiles for 256 CUs and stays out
-  {
-    static const bool no256 = getenv("SS_MLP_NO256") != nullptr;
-    const long long tiles = (long long)((M + 255) / 256) * ((N + 255) / 256);
-    if (!no256 && !y_is_f32 && tiles >= 230 && N % 256 == 0 && K >= 256 && K % 128 == 0 && (long long)M * K < (1ll << 32) && (long long)N * K < (1ll << 32)) {
-      LinearTrainArgs a{X, Wt, bias, nullptr, y, nullptr, nullptr, M, N, K, ldy, 0, act, 1, 1};
-      auto kern_ = ss_gemm256_kernel<G256_PLAIN>;
-      const size_t epi_ = (size_t)gemm256::TILE * (gemm256::TILE + 8) * sizeof(__bf16);
-      if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize, (int)epi_) != hipSuccess) return fail(SS_ERR_HIP, "cannot size the GEMM's LDS");
-      note_gemm("gemm256", 256, 64, 8, "bf16", "PLAIN", 1, 0);
-      hipLaunchKernelGGL(kern_, dim3((N + 255) / 256, (M + 255) / 256, 1), dim3(512), epi_, st, a);
-      hipError_t e = hipGetLastError();
-      return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
-    }
+  int remap = 1;   // XCD-aware tile order
+  const GemmPlan p = plan_linear(M, N, K, y_is_f32);
+  if (p.family == GEMM_256) {
+    LinearTrainArgs a{X, Wt, bias, nullptr, y, nullptr, nullptr, M, N, K, ldy, 0, act, remap, 1};
+    void *args[] = {&a};
+    return launch_gemm(p, args, (hipStream_t)stream);
   }
-  const int gm = (M + BM - 1) / BM;
-  // Tile width: the one whose tile count fills the chip's 256 CUs in whole rounds (4096 x 2048 -> 256 columns, x 1536 -> 192, x 1024 ->
-  // 128, x 512 -> 64: exactly one 128-row tile per CU each; round 3 used 128 x 128 for the two widest layers = 1.5 rounds of
-  // workgroups, a third of the chip idle in the second), ties to the wider tile (more MFMAs per LDS byte and per barrier)
-  static const char *force_bn = getenv("SS_MLP_BN");            // A/B switches (tools/gpu_mlp.py)
-  static const bool force32 = getenv("SS_MLP_BK32") != nullptr;
-  static const int remap = getenv("SS_MLP_NOREMAP") ? 0 : 1;
-  static const bool waves8 = getenv("SS_MLP_WAVES4") == nullptr;   // 8 waves per workgroup (32 x BN/2 each): twice the waves per SIMD
-  const bool k64 = K % 64 == 0 && !force32;
-  int bn = 64;
-  {
-    double best = -1;
-    const int cand[4] = {256, 192, 128, 64};
-    for (int c = 0; c < 4; c++) {
-      if ((!(k64 && waves8) || K < 512) && cand[c] > 128) continue;   // the wide tiles: 8-wave, K-tile-of-64 flavour only, and only for a deep K
-                                                                      // (289 -> 2048 has 5 K tiles: the 256-column tile's longer prologue / epilogue made it 24 vs 18 us)
-      if (cand[c] > 64 && N < cand[c]) continue;
-      const long long tiles = (long long)((N + cand[c] - 1) / cand[c]) * gm, rounds = (tiles + 255) / 256;
-      const double fill = (double)tiles / (double)(rounds * 256) * ((double)N / (double)(((N + cand[c] - 1) / cand[c]) * cand[c]));
-      if (fill > best + 1e-9) { best = fill; bn = cand[c]; }
-    }
-    if (force_bn && atoi(force_bn) > 0) bn = atoi(force_bn);
-  }
-  static const bool glds = getenv("SS_MLP_NOGLDS") == nullptr;   // round 5: asynchronous global -> LDS copies, three K tiles in flight
-#define SS_LAUNCH(BN_, BK_, F32_)                                                                                              \
-  do {                                                                                                                         \
-    dim3 grid((N + BN_ - 1) / BN_, gm);                                                                                        \
-    const size_t loop_ = (size_t)2 * (BM + BN_) * (BK_ + 8) * sizeof(__bf16), tile_ = (size_t)BM * (BN_ + 8) * sizeof(__bf16);   \
-    const size_t lds_ = loop_ > tile_ ? loop_ : tile_;   /* K loop's two stages; the epilogue stages the output tile in the same memory */ \
-    if (waves8 && BK_ == 64 && glds && K >= 512) {   /* (a shallow K keeps the two-stage kernel: two workgroups per CU hide its short loop better) */                                                                                         \
-      auto kern_ = ss_linear_glds_kernel<BN_, F32_>;                                                                           \
-      const size_t l3_ = (size_t)3 * (BM + BN_) * 64 * sizeof(__bf16);                                                         \
-      if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3_) != hipSuccess) return fail(SS_ERR_HIP, "cannot size the GEMM's LDS"); \
-      note_gemm("glds", BN_, 64, 8, F32_ ? "f32" : "bf16", "-", 1, 0);                                                      \
-      hipLaunchKernelGGL(kern_, grid, dim3(512), l3_, st, X, Wt, bias, y, M, N, K, ldy, act, remap);                            \
-    } else if (waves8 && BK_ == 64) {                                                                                          \
-      auto kern_ = ss_linear_kernel<BN_, BK_, F32_, 4>;                                                                        \
-      /* per launch: the attribute belongs to the (kernel, device) pair and the call is a table write (a process-wide flag left */ \
-      /* the wide tiles of a second GPU at the 64 KB default: ADVICE r4) */                                                     \
-      if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_) != hipSuccess) return fail(SS_ERR_HIP, "cannot size the GEMM's LDS"); \
-      note_gemm("linear", BN_, BK_, 8, F32_ ? "f32" : "bf16", "-", 1, 0);                                                   \
-      hipLaunchKernelGGL(kern_, grid, dim3(512), lds_, st, X, Wt, bias, y, M, N, K, ldy, act, remap);                           \
-    } else {                                                                                                                   \
-      auto kern_ = ss_linear_kernel<(BN_ > 128 ? 128 : BN_), BK_, F32_, 2>;                                                     \
-      if ((size_t)2 * (BM + (BN_ > 128 ? 128 : BN_)) * (BK_ + 8) * sizeof(__bf16) > 64 * 1024 &&                                  \
-          hipFuncSetAttribute(reinterpret_cast<const void *>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize,                \
-                              (int)((size_t)2 * (BM + (BN_ > 128 ? 128 : BN_)) * (BK_ + 8) * sizeof(__bf16))) != hipSuccess) return fail(SS_ERR_HIP, "cannot size the GEMM's LDS"); \
-      const size_t l4a_ = (size_t)2 * (BM + (BN_ > 128 ? 128 : BN_)) * (BK_ + 8) * sizeof(__bf16), l4b_ = (size_t)BM * ((BN_ > 128 ? 128 : BN_) + 8) * sizeof(__bf16); \
-      note_gemm("linear", BN_ > 128 ? 128 : BN_, BK_, 4, F32_ ? "f32" : "bf16", "-", 1, 0);                                 \
-      hipLaunchKernelGGL(kern_, dim3((N + (BN_ > 128 ? 128 : BN_) - 1) / (BN_ > 128 ? 128 : BN_), gm), dim3(256),              \
-                         l4a_ > l4b_ ? l4a_ : l4b_, st, X, Wt, bias, y, M, N, K, ldy, act, remap);                              \
-    }                                                                                                                          \
-  } while (0)
-#define SS_PICK(BN_)                                                                                                           \
-  do {                                                                                                                         \
-    if (k64) { if (y_is_f32) SS_LAUNCH(BN_, 64, true); else SS_LAUNCH(BN_, 64, false); }                                       \
-    else { if (y_is_f32) SS_LAUNCH(BN_, 32, true); else SS_LAUNCH(BN_, 32, false); }                                           \
-  } while (0)
-  if (bn == 256) SS_PICK(256);
-  else if (bn == 192) SS_PICK(192);
-  else if (bn == 128) SS_PICK(128);
-  else SS_PICK(64);
-#undef SS_PICK
-#undef SS_LAUNCH
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
+  void *args[] = {&X, &Wt, &bias, &y, &M, &N, &K, &ldy, &act, &remap};
+  return launch_gemm(p, args, (hipStream_t)stream);
 }
 
 static int linear_train_impl(const void *x, const void *w, const float *bias, const void *mul, void *y, void *yt, void *dact, int32_t M, int32_t N, int32_t K,
@@ -971,118 +1015,21 @@ static int linear_train_impl(const void *x, const void *w, const float *bias, co
   if (act < SS_ACT_NONE || act > SS_ACT_RELU) return fail(SS_ERR_INVALID, "unknown activation");
   if (y_is_f32_accumulate && (yt || dact || mul || act != SS_ACT_NONE || !y)) return fail(SS_ERR_INVALID, "ss_linear_bf16_train: the accumulating fp32 form has no other outputs, operand or activation");
   if ((mul || dact) && !y) return fail(SS_ERR_INVALID, "ss_linear_bf16_train: mul / dact share y's row stride: y must be given");
-  hipStream_t st = (hipStream_t)stream;
-  const int gm = (M + BM - 1) / BM;
-  static const int remap = getenv("SS_MLP_NOREMAP") ? 0 : 1;
-  // tile width as in ss_linear_bf16 (whole rounds of the 256 CUs), then the K split: products whose output has fewer tiles than CUs and a deep
-  // contraction (the weight gradients: K = the batch) are cut along K into as many shares as fill about two rounds
-  int bn = 64;
-  {
-    double best = -1;
-    const int cand[4] = {256, 192, 128, 64};
-    for (int c = 0; c < 4; c++) {
-      if (cand[c] > 64 && N < cand[c]) continue;
-      if (cand[c] > 128 && K < 512) continue;
-      const long long tiles = (long long)((N + cand[c] - 1) / cand[c]) * gm, rounds = (tiles + 255) / 256;
-      // (the accumulating form fills the chip with its K split: only the columns wasted by the last tile count)
-      // ... and so does a batch of thousands of rows: there the widest tile wins on every product measured (profiles/r06_train_gemm_sweep.txt)
-      const double fill = ((y_is_f32_accumulate || gm >= 64) ? 1.0 : (double)tiles / (double)(rounds * 256)) * ((double)N / (double)(((N + cand[c] - 1) / cand[c]) * cand[c]));
-      if (fill > best + 1e-9) { best = fill; bn = cand[c]; }
-    }
-    static const char *force_bn = getenv("SS_MLP_TRAIN_BN");
-    if (force_bn && atoi(force_bn) > 0) bn = atoi(force_bn);
-    { const char *live = getenv("SS_MLP_TRAIN_BN_LIVE"); if (live && atoi(live) > 0) bn = atoi(live); }   // (tools/gpu_train_gemm_sweep.py: re-read per call)
-  }
-  int ksplit = 1;
-  if (y_is_f32_accumulate) {
-    const long long tiles = (long long)((N + bn - 1) / bn) * gm;
-    const int nkt = K / 64;
-    ksplit = (int)((512 + tiles - 1) / tiles);
-    if (ksplit > nkt / 8) ksplit = nkt / 8 > 0 ? nkt / 8 : 1;   // at least 8 K tiles per share
-    if (ksplit < 1) ksplit = 1;
-    static const char *force_ks = getenv("SS_MLP_TRAIN_KSPLIT");
-    if (force_ks && atoi(force_ks) > 0) ksplit = atoi(force_ks);
-  }
-  LinearTrainArgs a{static_cast<const __bf16 *>(x), static_cast<const __bf16 *>(w), bias, static_cast<const __bf16 *>(mul), y, static_cast<__bf16 *>(yt),
-                    static_cast<__bf16 *>(dact), M, N, K, ldy, ldyt, act, remap, ksplit};
-  // the 256 x 256 kernel (ss_gemm256.h): products with thousands of rows or a K split to fill the chip with; its source offsets are 32-bit
+  // the 256 x 256 kernel (ss_gemm256.h): products with thousands of rows or a K split to fill the chip with
   // (measured, profiles/r06_gemm256.txt: thousands of rows -> 1.5-2 x the 128-row kernel; weight gradients with the batch as K -> 1.05-2.2 x once the K split fills ONE round)
   // the set of outputs it is built for (the other combinations keep the 128-row kernel)
   const int mode256 = y_is_f32_accumulate ? G256_ACCUM : (y && !mul && !yt && !dact) ? G256_PLAIN : (y && !mul && yt && dact) ? G256_FWD : (y && mul && yt && !dact) ? G256_DX :
                       (y && !mul && !yt && dact) ? G256_FWDN : (y && mul && !yt && !dact) ? G256_DXN : -1;
-  bool big = mode256 >= 0 && N >= 256 && M >= 256 && K >= 128 && K % 128 == 0 && (long long)M * K < (1ll << 32) && (long long)N * K < (1ll << 32) &&
-             (y_is_f32_accumulate ? K >= 8192 : M >= 2048);
-  { const char *live = getenv("SS_MLP_TRAIN_256"); if (live) big = atoi(live) != 0 && mode256 >= 0 && K >= 128 && K % 128 == 0 && (long long)M * K < (1ll << 32) && (long long)N * K < (1ll << 32); }
+  const bool big = mode256 >= 0 && N >= 256 && M >= 256 && fits_256(M, N, K) && (y_is_f32_accumulate ? K >= 8192 : M >= 2048);
   if (colsum && !(big && (mode256 == G256_DX || mode256 == G256_DXN)))
     return fail(SS_ERR_INVALID, "ss_linear_bf16_dx: column sums come from the 256 x 256 kernel only (M >= 2048, N >= 256, K a multiple of 128, mul and y given)");
-  if (big) {
-    a.colsum = colsum;
-    constexpr int T = gemm256::TILE;
-    const int gx = (N + T - 1) / T, gy = (M + T - 1) / T, nkt = K / 64;
-    int ks = 1;
-    if (y_is_f32_accumulate) {
-      // whole rounds of the 256 CUs (one workgroup per CU): as many shares as fill ONE round — 28 tiles x 19 shares = 532 workgroups ran as three rounds
-      int rounds = 1;
-      { const char *rd = getenv("SS_MLP_TRAIN_ROUNDS"); if (rd && atoi(rd) > 0) rounds = atoi(rd); }
-      ks = (int)(((long long)256 * rounds) / ((long long)gx * gy));
-      if (ks < 1) ks = 1;
-      if (ks > nkt / 8) ks = nkt / 8 > 0 ? nkt / 8 : 1;
-      static const char *force_ks = getenv("SS_MLP_TRAIN_KSPLIT");
-      if (force_ks && atoi(force_ks) > 0) ks = atoi(force_ks);
-      if (ks > nkt / 2) ks = nkt / 2;
-      int per = (nkt + ks - 1) / ks;
-      per += per & 1;                                         // shares of an even number of K tiles (nkt is even: the last share too)
-      ks = (nkt + per - 1) / per;
-      a.kper = per;
-    }
-    a.ksplit = ks;
-#ifdef SS_GEMM256_ABLATE
-    { const char *ab = getenv("SS_GEMM256_KLOOP_ONLY"); if (ab && atoi(ab)) a.xcd_remap |= 2 * atoi(ab); }
-#endif
-    dim3 grid(gx, gy, ks);
-    const size_t loop_ = gemm256::LOOP_LDS_BYTES, epi_ = (size_t)T * (T + 8) * sizeof(__bf16);
-#define SS_G256(MODE_, LDS_)                                                                                                   \
-    do {                                                                                                                       \
-      auto kern_ = ss_gemm256_kernel<MODE_>;                                                                                   \
-      if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_)) != hipSuccess) return fail(SS_ERR_HIP, "cannot size the GEMM's LDS"); \
-      note_gemm("gemm256", 256, 64, 8, MODE_ == G256_ACCUM ? "f32acc" : "bf16", &#MODE_[5], a.ksplit, a.kper);                \
-      hipLaunchKernelGGL(kern_, grid, dim3(512), LDS_, st, a);                                                                 \
-    } while (0)
-    if (y_is_f32_accumulate) SS_G256(G256_ACCUM, loop_);
-    else if (mode256 == G256_PLAIN) SS_G256(G256_PLAIN, epi_);
-    else if (mode256 == G256_FWD) SS_G256(G256_FWD, epi_);
-    else if (mode256 == G256_DX) SS_G256(G256_DX, epi_);
-    else if (mode256 == G256_FWDN) SS_G256(G256_FWDN, epi_);
-    else SS_G256(G256_DXN, epi_);
-#undef SS_G256
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
-  }
-#define SS_TRAIN(BN_)                                                                                                          \
-  do {                                                                                                                         \
-    dim3 grid((N + BN_ - 1) / BN_, gm, ksplit);                                                                                \
-    const size_t loop_ = (size_t)3 * (BM + BN_) * 64 * sizeof(__bf16);                                                         \
-    const size_t epi_ = ((size_t)BM * (BN_ + 8) > (size_t)BN_ * (BM + 8) ? (size_t)BM * (BN_ + 8) : (size_t)BN_ * (BM + 8)) * sizeof(__bf16); \
-    const size_t lds_ = loop_ > epi_ ? loop_ : epi_;                                                                           \
-    if (y_is_f32_accumulate) {                                                                                                 \
-      auto kern_ = ss_linear_train_kernel<BN_, true>;                                                                          \
-      if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize, (int)loop_) != hipSuccess) return fail(SS_ERR_HIP, "cannot size the GEMM's LDS"); \
-      note_gemm("train", BN_, 64, 8, "f32acc", "-", ksplit, (K / 64 + ksplit - 1) / ksplit);                                \
-      hipLaunchKernelGGL(kern_, grid, dim3(512), loop_, st, a);                                                                \
-    } else {                                                                                                                   \
-      auto kern_ = ss_linear_train_kernel<BN_, false>;                                                                         \
-      if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_) != hipSuccess) return fail(SS_ERR_HIP, "cannot size the GEMM's LDS"); \
-      note_gemm("train", BN_, 64, 8, "bf16", "-", 1, 0);                                                                    \
-      hipLaunchKernelGGL(kern_, grid, dim3(512), lds_, st, a);                                                                 \
-    }                                                                                                                          \
-  } while (0)
-  if (bn == 256) SS_TRAIN(256);
-  else if (bn == 192) SS_TRAIN(192);
-  else if (bn == 128) SS_TRAIN(128);
-  else SS_TRAIN(64);
-#undef SS_TRAIN
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
+  const GemmPlan p = big ? plan_256(M, N, K, mode256) : plan_train(M, N, K, y_is_f32_accumulate);
+  LinearTrainArgs a{static_cast<const __bf16 *>(x), static_cast<const __bf16 *>(w), bias, static_cast<const __bf16 *>(mul), y, static_cast<__bf16 *>(yt),
+                    static_cast<__bf16 *>(dact), M, N, K, ldy, ldyt, act, 1, p.ksplit};
+  a.kper = big ? p.kper : 0;   // (the 128-row kernel derives its share from ksplit)
+  a.colsum = colsum;
+  void *args[] = {&a};
+  return launch_gemm(p, args, (hipStream_t)stream);
 }
 
 int ss_linear_bf16_train(const void *x, const void *w, const float *bias, const void *mul, void *y, void *yt, void *dact, int32_t M, int32_t N, int32_t K,
@@ -1102,19 +1049,13 @@ int ss_wgrad_bf16(const void *dz, const void *h, float *dw, int32_t Mb, int32_t 
     return fail(SS_ERR_INVALID, "ss_wgrad_bf16: the batch a multiple of 128 rows; n_out, n_in, ldz, ldh multiples of 8; 16-byte aligned operands; ldw >= n_in");
   if ((long long)Mb * ldz >= (1ll << 32) || (long long)Mb * ldh >= (1ll << 32)) return fail(SS_ERR_INVALID, "ss_wgrad_bf16: operands beyond 2^32 elements");
   const int gx = (n_in + 255) / 256, gy = (n_out + 255) / 256, nkt = Mb / 64;
-  int ks = (int)(256ll / ((long long)gx * gy));               // K shares that fill one round of the CUs (one workgroup per CU)
-  if (ks < 1) ks = 1;
-  if (ks > nkt / 8) ks = nkt / 8 > 0 ? nkt / 8 : 1;
-  int per = (nkt + ks - 1) / ks;
-  per += per & 1;                                             // shares of an even number of K tiles (nkt is even)
-  ks = (nkt + per - 1) / per;
-  WgradArgs a{static_cast<const __bf16 *>(dz), static_cast<const __bf16 *>(h), dw, n_out, n_in, ldz, ldh, ldw, nkt, per};
-  const size_t lds = gemm256::LoopTN::LDS_BYTES;
-  if (hipFuncSetAttribute(reinterpret_cast<const void *>(ss_wgrad_tn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return fail(SS_ERR_HIP, "cannot size the GEMM's LDS");
-  note_gemm("wgrad", 256, 64, 8, "f32acc", "-", ks, per);
-  hipLaunchKernelGGL(ss_wgrad_tn_kernel, dim3(gx, gy, ks), dim3(512), lds, (hipStream_t)stream, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
+  GemmPlan p{GEMM_WGRAD, true};
+  split_256(p, (long long)gx * gy, nkt);
+  p.grid = dim3(gx, gy, p.ksplit);
+  p.lds = gemm256::LoopTN::LDS_BYTES;
+  WgradArgs a{static_cast<const __bf16 *>(dz), static_cast<const __bf16 *>(h), dw, n_out, n_in, ldz, ldh, ldw, nkt, p.kper};
+  void *args[] = {&a};
+  return launch_gemm(p, args, (hipStream_t)stream);
 }
 
 int ss_debug_last_gemm(char *buf, int32_t len) {

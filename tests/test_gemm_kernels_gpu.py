@@ -389,7 +389,7 @@ def test_linear_bf16_train_128_row_kernel_every_output_subset(shape, bn):
     ("FWDN", (4096, 256, 128), "y d", False), ("FWD", (4100, 1000, 640), "y yt d", True), ("DX", (4100, 1000, 640), "y m yt", False),
     ("DXN", (2048, 300, 384), "y m", True), ("PLAIN", (2049, 512, 128), "y", True)])
 def test_gemm256_modes_at_natural_shapes(mode, shape, outs, scalar):
-    """The 256 x 256 kernel's bf16 modes as the dispatch picks them without SS_MLP_TRAIN_256: ragged M (256 k + 4, 256 k + 1) and N (not a multiple
+    """The 256 x 256 kernel's bf16 modes as the dispatch picks them: ragged M (256 k + 4, 256 k + 1) and N (not a multiple
     of the tile, N = 300 not a multiple of 8), vector and edge stores, a bias, two launches bit-identical."""
     M, N, K = shape
     x, w, b = _operands(M, N, K, seed=M + 3 * N + K)

@@ -1096,17 +1096,18 @@ def _last_gemm():
     return buf.value.decode()
 
 
-@pytest.mark.parametrize("M,N,K,act", [(2048, 1536, 2048, "silu"), (300, 260, 128, "tanh"), (4096, 512, 1024, "none"), (1000, 1000, 384, "relu")])
-def test_gemm256_kernel_outputs(M, N, K, act, monkeypatch):
+@pytest.mark.parametrize("M,N,K,act", [(2048, 1536, 2048, "silu"), (2092, 260, 128, "tanh"), (4096, 512, 1024, "none"), (2280, 1000, 384, "relu")])
+def test_gemm256_kernel_outputs(M, N, K, act):
     """The 256 x 256 macro-tile kernel behind ss_linear_bf16_train (csrc/ss_gemm256.h: staggered wave rows, copies in flight across barriers):
     the same three outputs against torch on asymmetric bf16 operands, ragged M and N, the shortest K loop it takes (two K tiles), and the same
     bits from every one of 20 launches (a copy that lands after its reader shows up as a launch that differs).  Without the multiplying operand
     the forward mode (y, y^T, act'); with it the dX mode (y, y^T); y, y^T and act' WITH the operand is not a mode of the 256 x 256 kernel and
-    falls back to the 128-row kernel (checked against the same reference)."""
+    falls back to the 128-row kernel (checked against the same reference).  Every shape has the thousands of rows that send the dispatch to the
+    256 x 256 kernel by itself.  The accumulating form runs on operands of its own with K = 8320 (at least 8192, 130 K tiles): shares of an even
+    number of K tiles, a shorter last share at (4096, 512) and (2280, 1000)."""
     import ctypes as C
     from smplsim_amd import _cabi
     from smplsim_amd._lib import lib
-    monkeypatch.setenv("SS_MLP_TRAIN_256", "1")
     g = torch.Generator().manual_seed(M + N + K)
     x = (torch.randn(M, K, generator=g) * 0.5 + torch.linspace(-1, 1, K)[None, :] * 0.3).to(torch.bfloat16).cuda()
     w = (torch.randn(N, K, generator=g) / K ** 0.5 + torch.linspace(-1, 1, N)[:, None] * 0.02).to(torch.bfloat16).cuda()
@@ -1142,8 +1143,12 @@ def test_gemm256_kernel_outputs(M, N, K, act, monkeypatch):
             else:
                 assert torch.equal(y, first[0]) and torch.equal(yt, first[1]) and (not use_d or torch.equal(d, first[2])), rep
     # the accumulating form: K split into shares of an even number of tiles, against the fp32 product
+    Ka = 8320
+    x = (torch.randn(M, Ka, generator=g) * 0.5 + torch.linspace(-1, 1, Ka)[None, :] * 0.3).to(torch.bfloat16).cuda()
+    w = (torch.randn(N, Ka, generator=g) / Ka ** 0.5 + torch.linspace(-1, 1, N)[:, None] * 0.02).to(torch.bfloat16).cuda()
     yf = torch.zeros(M, N + 3, device="cuda")
-    assert lib().ss_linear_bf16_train(ptr(x), ptr(w), None, None, ptr(yf), None, None, M, N, K, N + 3, 0, 0, 1, st) == 0
+    assert lib().ss_linear_bf16_train(ptr(x), ptr(w), None, None, ptr(yf), None, None, M, N, Ka, N + 3, 0, 0, 1, st) == 0
+    assert _last_gemm().startswith("gemm256 mode=ACCUM "), _last_gemm()
     torch.cuda.synchronize()
     ref = x.float() @ w.float().T
     assert (yf[:, N:] == 0).all()

@@ -5,7 +5,6 @@ import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from smplsim_amd._lib import lib
-os.environ["SS_MLP_TRAIN_256"] = "1"
 REPS = int(os.environ.get("REPS", "100"))
 ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
 st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
