@@ -34,7 +34,8 @@ int ss_linear_bf16(const void *x, const void *w, const float *bias, void *y, int
  *       NULL (mul and dact need y).
  *   accumulating fp32 form (y_is_f32_accumulate = 1):  y [M, ldy] fp32 += x W^T (+ bias), the contraction split over several workgroups whose
  *       partial sums meet in y by hardware atomics — for products with few outputs and a deep K (the weight gradients: K = the batch).
- *       The caller zeroes y. */
+ *       The caller zeroes y.  This form has no deterministic twin: its result depends on the order in which the workgroups' atomics arrive; the update
+ *       no longer calls it (weight gradients go through ss_wgrad_bf16, which has one: ss_wgrad_bf16_det). */
 int ss_linear_bf16_train(const void *x, const void *w, const float *bias, const void *mul, void *y, void *yt, void *dact, int32_t M, int32_t N,
                          int32_t K, int32_t ldy, int32_t ldyt, int32_t activation, int32_t y_is_f32_accumulate, void *stream);
 
@@ -50,12 +51,39 @@ int ss_obs_to_bf16(const float *obs, int32_t M, int32_t dim, int32_t obs_stride,
  * Served by the 256 x 256 kernel only: M >= 2048, N >= 256, K a multiple of 128 (SS_ERR_INVALID otherwise: use ss_linear_bf16_train and sum the columns yourself). */
 int ss_linear_bf16_dx(const void *x, const void *w, const void *mul, void *y, float *colsum, int32_t M, int32_t N, int32_t K, int32_t ldy, void *stream);
 
+/* ss_linear_bf16_dx with reproducible column sums: same contract and shape limits (colsum += ; y is bit-identical to ss_linear_bf16_dx's), and the result is a
+ * function of the arguments and the input bytes alone — not of the order in which workgroups run, nor of what the workspace held before.
+ *   workspace  caller-owned, 16-byte aligned, at least ss_linear_bf16_dx_det_workspace(M, N, K) = 2 * ceil(M / 256) * N * 4 bytes.  After the call it holds
+ *              P = 2 * ceil(M / 256) rows of N floats, dense: row p, column j is the fp32 sum of the result's column j over the rows [128 p, min(128 p + 128, M))
+ *              (zero for a p whose rows all lie beyond M), formed inside one wavefront in an order fixed by the kernel.
+ *   order      colsum[j] += (((P_0[j] + P_1[j]) + P_2[j]) + ... + P_{P-1}[j]): the sum over the partial rows first, ascending, in fp32, starting from
+ *              row 0; then one addition to colsum[j].  Two launches on `stream` (the product, the reduce); the workspace may be reused by the next call on
+ *              the same stream.
+ * SS_ERR_INVALID (nothing launched) for a null, misaligned or too-small workspace.  The query returns a negative value for shapes ss_linear_bf16_dx rejects. */
+int ss_linear_bf16_dx_det(const void *x, const void *w, const void *mul, void *y, float *colsum, int32_t M, int32_t N, int32_t K, int32_t ldy, void *workspace,
+                          int64_t workspace_bytes, void *stream);
+int64_t ss_linear_bf16_dx_det_workspace(int32_t M, int32_t N, int32_t K);
+
 /* Weight gradient of a linear layer from the two tensors as autograd holds them (replaces `grad_W = dZ^T @ h` of torch.nn.Linear's backward inside the
  * reference's update_policy / update_value, agents/agent_ppo.py:20-83):
  *   dw[i, j] += sum_m dz[m, i] * h[m, j]      dz [Mb, ldz] bf16 (columns 0 .. n_out - 1 used), h [Mb, ldh] bf16 (columns 0 .. n_in - 1), dw [n_out, ldw] fp32
  * Both operands are read untransposed (contraction over their ROWS); the caller zeroes dw; partial sums of a K split meet by fp32 atomics.
  * Mb a multiple of 128 (pad rows zero), n_out, n_in, ldz, ldh multiples of 8, dz and h 16-byte aligned, ldw >= n_in. */
 int ss_wgrad_bf16(const void *dz, const void *h, float *dw, int32_t Mb, int32_t n_out, int32_t n_in, int32_t ldz, int32_t ldh, int32_t ldw, void *stream);
+
+/* ss_wgrad_bf16 with a reproducible result: same contract (dw += , the same alignment and size rules), and dw is a function of the arguments and the input
+ * bytes alone.  The batch is cut into the same S shares of `kper` K tiles (64 rows each) as ss_wgrad_bf16 cuts it (S = ksplit of ss_debug_last_gemm:
+ * min(256 / output tiles of 256 x 256, Mb / 512) shares, at least 1, rounded so that every share holds an even number of K tiles; no share is empty).
+ *   workspace  caller-owned, 16-byte aligned, at least ss_wgrad_bf16_det_workspace(Mb, n_out, n_in) = S * n_out * n_in * 4 bytes.  After the call partial s lies
+ *              dense at workspace + s * n_out * n_in floats, row-major [n_out, n_in]: the product over the rows [s * kper * 64, min((s + 1) * kper * 64, Mb))
+ *              of dz and h, written by plain stores (no atomics; dw is not read by the product).
+ *   order      dw[i, j] += (((p_0[i, j] + p_1[i, j]) + p_2[i, j]) + ... + p_{S-1}[i, j]): the sum over the shares first, ascending, in fp32, starting from
+ *              p_0; then one addition to dw[i, j].  The padding of dw (columns n_in .. ldw - 1) is not touched.  Two launches on `stream`; the workspace may be
+ *              reused by the next call on the same stream.
+ * SS_ERR_INVALID (nothing launched) for a null, misaligned or too-small workspace.  The query returns a negative value for invalid arguments. */
+int ss_wgrad_bf16_det(const void *dz, const void *h, float *dw, int32_t Mb, int32_t n_out, int32_t n_in, int32_t ldz, int32_t ldh, int32_t ldw, void *workspace,
+                      int64_t workspace_bytes, void *stream);
+int64_t ss_wgrad_bf16_det_workspace(int32_t Mb, int32_t n_out, int32_t n_in);
 
 /* The Gaussian head of the sampler in one launch (PolicyGaussian.select_action, policy_gaussian.py:25-41 -> DiagGaussian.sample;
  * Agent.preprocess_actions with clip_actions, agents/agent.py:153-161; normal_log_density of get_log_prob): per row
@@ -66,9 +94,10 @@ int ss_wgrad_bf16(const void *dz, const void *h, float *dw, int32_t Mb, int32_t 
 int ss_gaussian_sample(const float *mean, const float *noise, const float *log_std, int32_t M, int32_t dim, float *action, int32_t lda,
                        float *action_env, int32_t lde, float clip_lo, float clip_hi, float *logp, void *stream);
 
-/* Test hook: the GEMM instantiation launched last by an ss_linear_* / ss_wgrad_bf16 call on the calling host thread, as
- * "<family> mode=<G256 mode or -> bn=<BN> bk=<BK> waves=<waves per workgroup> out=<bf16|f32|f32acc> ksplit=<K shares> kper=<K tiles per share>"
- * with family linear / glds / train / gemm256 / wgrad (empty before the first launch).  Copies it, NUL-terminated and truncated to len - 1
+/* Test hook: the GEMM instantiation launched last by an ss_linear_* / ss_wgrad_bf16* call on the calling host thread, as
+ * "<family> mode=<G256 mode or -> bn=<BN> bk=<BK> waves=<waves per workgroup> out=<bf16|f32|f32acc|f32det> ksplit=<K shares> kper=<K tiles per share>"
+ * with family linear / glds / train / gemm256 / wgrad (empty before the first launch).  The deterministic entries report their GEMM, not their reduce pass:
+ * ss_wgrad_bf16_det with out=f32det, ss_linear_bf16_dx_det the line of ss_linear_bf16_dx with " colsum=det" appended.  Copies it, NUL-terminated and truncated to len - 1
  * characters, into buf; returns its full length. */
 int ss_debug_last_gemm(char *buf, int32_t len);
 

@@ -47,6 +47,7 @@ class PPOConfig:
     amp_bf16: bool = False      # run the update's network passes under bf16 autocast (MFMA rate); off = the reference's fp32
     mfma_inference: bool = False   # sampler: policy forward by the library's fused bf16 MFMA kernels (learning/fast_policy.py)
     mfma_update: bool = False      # update: the networks' forward AND backward passes on the library's own GEMM (learning/fused_train.py), bf16 operands
+    deterministic_update: bool = False   # with mfma_update: the update's reductions in a fixed order (same seed, same bits; DESIGN.md "deterministic update")
     extra: dict = field(default_factory=dict)
 
 
@@ -55,6 +56,8 @@ class AgentPPO:
         self.env, self.cfg = env, cfg or PPOConfig()
         c = self.cfg
         self.device = env.device
+        if c.deterministic_update and not c.mfma_update:
+            raise ValueError("deterministic_update applies to the mfma_update path only (the torch update paths are reproducible as they are)")
         torch.manual_seed(seed)
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed)
@@ -75,8 +78,8 @@ class AgentPPO:
         self.fused_policy = self.fused_value = None
         if c.mfma_update:
             from ..learning.fused_train import FusedMLPTrain
-            self.fused_policy = FusedMLPTrain(self.policy_net.net.affine_layers, self.policy_net.action_mean, c.activation)
-            self.fused_value = FusedMLPTrain(self.value_net.net.affine_layers, self.value_net.value_head, c.activation)
+            self.fused_policy = FusedMLPTrain(self.policy_net.net.affine_layers, self.policy_net.action_mean, c.activation, deterministic=c.deterministic_update)
+            self.fused_value = FusedMLPTrain(self.value_net.net.affine_layers, self.value_net.value_head, c.activation, deterministic=c.deterministic_update)
 
     # ------------------------------------------------------------------ sampling
     def _prep_obs(self, obs):

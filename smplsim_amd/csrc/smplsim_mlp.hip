@@ -371,7 +371,8 @@ struct LinearTrainArgs {
   __bf16 *Dact;                 // [M, ldy] act'(pre-activation) or null
   int M, N, K, ldy, ldyt, act, xcd_remap, ksplit;
   int kper = 0;                 // ss_gemm256_kernel: K tiles per share (even; the host's number, not re-derived from ksplit)
-  float *colsum = nullptr;      // ss_gemm256_kernel with `mul`: [N] += column sums of the fp32 result (the bias gradient of the layer below)
+  float *colsum = nullptr;      // ss_gemm256_kernel with `mul`: [N] += column sums of the fp32 result (the bias gradient of the layer below);
+                                // G256_DXN_DET: the [2 * ceil(M / 256), N] partial column sums, stored
 };
 
 template <int BN, bool F32ATOMIC>
@@ -557,7 +558,8 @@ __global__ void __launch_bounds__(512) ss_linear_train_kernel(const LinearTrainA
 // Why compile-time: the K loop alone runs the 53 248 x 1536 x 2048 product in 256 us = 1.31 PFLOP/s; the first epilogue (run-time `if (Y)`, `if (Dact)` per
 // element, one dependent exp -> rcp chain after the other between the branches, every 16-byte chunk of the output parked in scratch because its edge
 // path indexed it dynamically) cost 90 us for ONE image and 200 us for three (profiles/r06_gemm256.txt).
-enum { G256_ACCUM = 0, G256_PLAIN = 1, G256_FWD = 2, G256_DX = 3, G256_FWDN = 4, G256_DXN = 5 };   // ..N: without the transposed image (ss_wgrad_bf16 reads the operands as they lie)
+enum { G256_ACCUM = 0, G256_PLAIN = 1, G256_FWD = 2, G256_DX = 3, G256_FWDN = 4, G256_DXN = 5,     // ..N: without the transposed image (ss_wgrad_bf16 reads the operands as they lie)
+       G256_DXN_DET = 6 };   // G256_DXN whose column sums are STORED, one row of partials per wave row (128 rows of the batch), instead of added to colsum (ss_linear_bf16_dx_det)
 
 __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
   union { __bf16 h[2]; unsigned u; } c;
@@ -623,7 +625,7 @@ __global__ void __launch_bounds__(512) ss_gemm256_kernel(const LinearTrainArgs a
         }
     }
   } else {
-    constexpr bool HAS_MUL = MODE == G256_DX || MODE == G256_DXN, HAS_D = MODE == G256_FWD || MODE == G256_FWDN, HAS_T = MODE == G256_FWD || MODE == G256_DX;
+    constexpr bool HAS_MUL = MODE == G256_DX || MODE == G256_DXN || MODE == G256_DXN_DET, HAS_D = MODE == G256_FWD || MODE == G256_FWDN, HAS_T = MODE == G256_FWD || MODE == G256_DX;
     constexpr int CS = T + 8, CPR = T / 8;
     constexpr int HALF_IMG = 128 * CS;                        // elements of one half image (128 rows)
     __bf16 *Cs = lds_g;
@@ -676,7 +678,8 @@ __global__ void __launch_bounds__(512) ss_gemm256_kernel(const LinearTrainArgs a
         }
     }
     if constexpr (HAS_MUL) {
-      if (a.colsum) {
+      constexpr bool COLSUM_DET = MODE == G256_DXN_DET;       // a.colsum is the [2 * row tiles, N] image of partial sums: row 2 * (row tile) + (wave row), stored
+      if (COLSUM_DET || a.colsum) {
         // bias gradient of the layer below: the column sums of dZ, from the fp32 values in the accumulators (a lane holds 64 rows of each of its two columns;
         // its partner 32 lanes on holds the other 64 of this wave's 128), one atomic per column and wave
 #pragma unroll
@@ -691,7 +694,11 @@ __global__ void __launch_bounds__(512) ss_gemm256_kernel(const LinearTrainArgs a
             }
           sum += __shfl_xor(sum, 32, 64);
           const int col = n0 + col_l + tn * 32;
-          if (lane < 32 && col < N) unsafeAtomicAdd(a.colsum + col, sum);
+          if constexpr (COLSUM_DET) {
+            if (lane < 32 && col < N) a.colsum[(size_t)(2 * by + wr) * N + col] = sum;
+          } else {
+            if (lane < 32 && col < N) unsafeAtomicAdd(a.colsum + col, sum);
+          }
         }
       }
       __syncthreads();
@@ -779,7 +786,7 @@ __global__ void __launch_bounds__(512) ss_gemm256_kernel(const LinearTrainArgs a
 // gemm256::LoopTN (fragments by ds_read_b64_tr_b16); K split over one round of the CUs, fp32 atomics, as ss_gemm256_kernel<G256_ACCUM>.
 struct WgradArgs {
   const __bf16 *Z, *H;          // [Mb, ldz], [Mb, ldh]
-  float *dW;                    // [NI, ldw] += ; NI = columns of Z used, NJ = columns of H used
+  float *dW;                    // [NI, ldw] += ; NI = columns of Z used, NJ = columns of H used (deterministic form: the workspace, ldw = NJ)
   int NI, NJ, ldz, ldh, ldw, nkt, kper;
 };
 
@@ -810,6 +817,60 @@ __global__ void __launch_bounds__(512) ss_wgrad_tn_kernel(const WgradArgs a) {
         if (row < a.NI && col < a.NJ) unsafeAtomicAdd(a.dW + (size_t)row * a.ldw + col, acc[tm][tn][r]);
       }
   }
+}
+
+// ss_wgrad_bf16_det: the same K loop and K split, but the tile of partial sums of K share blockIdx.z is STORED into the share's own dense [NI, NJ] image of
+// the workspace (a.dW, a.ldw = NJ) instead of added to dW — no atomics, no read of the output; ss_reduce_shares_kernel then adds the images to dW in a fixed
+// order.  A share without K tiles stores zeros (split_256 leaves none; the reduce pass reads every share).  A kernel of its own, not a template parameter of
+// the one above: wrapped in a shared body the default kernel's scalar prologue came out in a different order.
+__global__ void __launch_bounds__(512) ss_wgrad_tn_det_kernel(const WgradArgs a) {
+  extern __shared__ __attribute__((aligned(16))) __bf16 lds_g[];
+  const int i0 = blockIdx.y * 256, j0 = blockIdx.x * 256;
+  const int kt0 = (int)blockIdx.z * a.kper, kt1 = kt0 + a.kper < a.nkt ? kt0 + a.kper : a.nkt, nkt = kt1 - kt0;
+  f32x16 acc[4][2];
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+  gemm256::LoopTN L;
+  L.init(a.Z, a.H, a.ldz, a.ldh, a.NI, a.NJ, i0, j0, kt0, reinterpret_cast<char *>(lds_g));
+  if (nkt >= 2 && !(nkt & 1)) L.run(acc, nkt);
+  const int lane = L.lane;
+  float *out = a.dW + (size_t)blockIdx.z * a.NI * a.NJ;
+#pragma unroll
+  for (int tn = 0; tn < 2; tn++) {
+    const int col = j0 + L.wc * 64 + tn * 32 + (lane & 31);
+#pragma unroll
+    for (int tm = 0; tm < 4; tm++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const int row = i0 + L.wr * 128 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (row < a.NI && col < a.NJ) out[(size_t)row * a.ldw + col] = acc[tm][tn][r];
+      }
+  }
+}
+
+// Fixed-order reduce of the deterministic forms: out[r, c] += ((p_0 + p_1) + p_2) + ... + p_{S-1} at [r, c], p_s the dense [rows, cols] image at
+// part + s * rows * cols.  The sum over the shares is formed first, in ascending share order, in fp32, starting from p_0; out (row stride ldo >= cols, its
+// padding untouched) is read and written once.  One element per thread; the loads of eight shares are issued together and only the additions form a chain.
+__global__ void __launch_bounds__(256) ss_reduce_shares_kernel(const float *__restrict__ part, float *__restrict__ out, int rows, int cols, int ldo, int S) {
+  const int n = rows * cols, idx = (int)blockIdx.x * 256 + threadIdx.x;   // (the host keeps rows * cols below 2^31)
+  if (idx >= n) return;
+  const float *p = part + idx;
+  float sum = p[0];
+  int s = 1;
+  for (; s + 8 <= S; s += 8) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) v[j] = p[(size_t)(s + j) * n];
+#pragma unroll
+    for (int j = 0; j < 8; j++) sum += v[j];
+  }
+  for (; s < S; s++) sum += p[(size_t)s * n];
+  float *o = out + (size_t)(idx / cols) * ldo + idx % cols;
+  *o += sum;
 }
 
 // torch.clamp semantics: a NaN stays a NaN (fminf / fmaxf would return the bound and hide a diverged policy or observation from the env)
@@ -861,6 +922,7 @@ struct GemmPlan {
   dim3 grid;
   size_t lds = 0;                     // dynamic LDS bytes
   int ksplit = 1, kper = 0;           // K shares over grid.z and 64-wide K tiles per share (the accumulating forms)
+  bool det = false;                   // GEMM_WGRAD: the shares' partial sums stored into a workspace (ss_wgrad_bf16_det) instead of added by atomics
 };
 
 // Tile width of the 128-row kernels: the one whose tile count fills the chip's 256 CUs in whole rounds (4096 x 2048 -> 256 columns, x 1536 ->
@@ -960,11 +1022,11 @@ const void *gemm_kernel(const GemmPlan &p) {
     return k[w][o];
   }
   case GEMM_256: {
-    static const F k[6] = {F(ss_gemm256_kernel<G256_ACCUM>), F(ss_gemm256_kernel<G256_PLAIN>), F(ss_gemm256_kernel<G256_FWD>), F(ss_gemm256_kernel<G256_DX>),
-                           F(ss_gemm256_kernel<G256_FWDN>), F(ss_gemm256_kernel<G256_DXN>)};
+    static const F k[7] = {F(ss_gemm256_kernel<G256_ACCUM>), F(ss_gemm256_kernel<G256_PLAIN>), F(ss_gemm256_kernel<G256_FWD>), F(ss_gemm256_kernel<G256_DX>),
+                           F(ss_gemm256_kernel<G256_FWDN>), F(ss_gemm256_kernel<G256_DXN>), F(ss_gemm256_kernel<G256_DXN_DET>)};
     return k[p.mode];
   }
-  case GEMM_WGRAD: return F(ss_wgrad_tn_kernel);
+  case GEMM_WGRAD: return p.det ? F(ss_wgrad_tn_det_kernel) : F(ss_wgrad_tn_kernel);
   }
   return nullptr;
 }
@@ -977,15 +1039,31 @@ int launch_gemm(const GemmPlan &p, void **args, hipStream_t st) {
   // per launch: the attribute belongs to the (kernel, device) pair and the call is a table write (a process-wide flag left
   // the wide tiles of a second GPU at the 64 KB default: ADVICE r4)
   if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds) != hipSuccess) return fail(SS_ERR_HIP, "cannot size the GEMM's LDS");
-  static const char *const family[] = {"glds", "linear", "train", "gemm256", "wgrad"}, *const mode[] = {"ACCUM", "PLAIN", "FWD", "DX", "FWDN", "DXN"};
+  static const char *const family[] = {"glds", "linear", "train", "gemm256", "wgrad"}, *const mode[] = {"ACCUM", "PLAIN", "FWD", "DX", "FWDN", "DXN", "DXN"};
   char b[160];
-  snprintf(b, sizeof b, "%s mode=%s bn=%d bk=%d waves=%d out=%s ksplit=%d kper=%d", family[p.family], p.family == GEMM_256 ? mode[p.mode] : "-", p.bn, p.bk,
-           p.waves, !p.f32 ? "bf16" : p.family <= GEMM_LINEAR ? "f32" : "f32acc", p.ksplit, p.kper);
+  snprintf(b, sizeof b, "%s mode=%s bn=%d bk=%d waves=%d out=%s ksplit=%d kper=%d%s", family[p.family], p.family == GEMM_256 ? mode[p.mode] : "-", p.bn, p.bk,
+           p.waves, !p.f32 ? "bf16" : p.family <= GEMM_LINEAR ? "f32" : p.det ? "f32det" : "f32acc", p.ksplit, p.kper, p.mode == G256_DXN_DET ? " colsum=det" : "");
   last_gemm = b;
   (void)hipLaunchKernel(kern, p.grid, dim3(64 * p.waves), args, p.lds, st);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
 }
+
+// the second launch of the deterministic forms (ss_debug_last_gemm keeps describing the GEMM)
+int launch_reduce(const float *part, float *out, int rows, int cols, int ldo, int S, hipStream_t st) {
+  hipLaunchKernelGGL(ss_reduce_shares_kernel, dim3((unsigned)((rows * cols + 255) / 256)), dim3(256), 0, st, part, out, rows, cols, ldo, S);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
+}
+
+int check_workspace(const void *ws, int64_t bytes, int64_t need) {
+  if (!ws) return fail(SS_ERR_INVALID, "deterministic form: null workspace");
+  if (reinterpret_cast<size_t>(ws) & 15) return fail(SS_ERR_INVALID, "deterministic form: the workspace must be 16-byte aligned");
+  if (bytes < need) return fail(SS_ERR_INVALID, "deterministic form: the workspace is too small (see the _workspace query)");
+  return SS_OK;
+}
+
+bool dx_served(int M, int N, int K) { return N >= 256 && M >= 2048 && fits_256(M, N, K); }   // ss_linear_bf16_dx: the 256 x 256 kernel only
 
 }  // namespace
 
@@ -1009,7 +1087,8 @@ int ss_linear_bf16(const void *x, const void *w, const float *bias, void *y, int
 }
 
 static int linear_train_impl(const void *x, const void *w, const float *bias, const void *mul, void *y, void *yt, void *dact, int32_t M, int32_t N, int32_t K,
-                             int32_t ldy, int32_t ldyt, int32_t act, int32_t y_is_f32_accumulate, float *colsum, void *stream) {
+                             int32_t ldy, int32_t ldyt, int32_t act, int32_t y_is_f32_accumulate, float *colsum, void *stream, bool det = false,
+                             void *colsum_ws = nullptr, int64_t colsum_ws_bytes = 0) {   // det: ss_linear_bf16_dx_det (partial column sums into colsum_ws, reduced into colsum by a second launch)
   if (!x || !w || (!y && !yt)) return fail(SS_ERR_INVALID, "null argument");
   if (M < 1 || N < 1 || K < 64 || K % 64 || (y && ldy < N) || (yt && ldyt < M)) return fail(SS_ERR_INVALID, "ss_linear_bf16_train: K must be a positive multiple of 64, ldy >= N, ldyt >= M");
   if (act < SS_ACT_NONE || act > SS_ACT_RELU) return fail(SS_ERR_INVALID, "unknown activation");
@@ -1023,13 +1102,17 @@ static int linear_train_impl(const void *x, const void *w, const float *bias, co
   const bool big = mode256 >= 0 && N >= 256 && M >= 256 && fits_256(M, N, K) && (y_is_f32_accumulate ? K >= 8192 : M >= 2048);
   if (colsum && !(big && (mode256 == G256_DX || mode256 == G256_DXN)))
     return fail(SS_ERR_INVALID, "ss_linear_bf16_dx: column sums come from the 256 x 256 kernel only (M >= 2048, N >= 256, K a multiple of 128, mul and y given)");
-  const GemmPlan p = big ? plan_256(M, N, K, mode256) : plan_train(M, N, K, y_is_f32_accumulate);
+  const int prows = 2 * ((M + 255) / 256);   // one row of partial column sums per 128 rows of the batch
+  if (det && check_workspace(colsum_ws, colsum_ws_bytes, (int64_t)prows * N * 4) != SS_OK) return SS_ERR_INVALID;
+  const GemmPlan p = big ? plan_256(M, N, K, det ? G256_DXN_DET : mode256) : plan_train(M, N, K, y_is_f32_accumulate);
   LinearTrainArgs a{static_cast<const __bf16 *>(x), static_cast<const __bf16 *>(w), bias, static_cast<const __bf16 *>(mul), y, static_cast<__bf16 *>(yt),
                     static_cast<__bf16 *>(dact), M, N, K, ldy, ldyt, act, 1, p.ksplit};
   a.kper = big ? p.kper : 0;   // (the 128-row kernel derives its share from ksplit)
-  a.colsum = colsum;
+  a.colsum = det ? static_cast<float *>(colsum_ws) : colsum;
   void *args[] = {&a};
-  return launch_gemm(p, args, (hipStream_t)stream);
+  const int rc = launch_gemm(p, args, (hipStream_t)stream);
+  if (rc != SS_OK || !det) return rc;
+  return launch_reduce(a.colsum, colsum, 1, N, N, prows, (hipStream_t)stream);
 }
 
 int ss_linear_bf16_train(const void *x, const void *w, const float *bias, const void *mul, void *y, void *yt, void *dact, int32_t M, int32_t N, int32_t K,
@@ -1042,7 +1125,22 @@ int ss_linear_bf16_dx(const void *x, const void *w, const void *mul, void *y, fl
   return linear_train_impl(x, w, nullptr, mul, y, nullptr, nullptr, M, N, K, ldy, 0, SS_ACT_NONE, 0, colsum, stream);
 }
 
-int ss_wgrad_bf16(const void *dz, const void *h, float *dw, int32_t Mb, int32_t n_out, int32_t n_in, int32_t ldz, int32_t ldh, int32_t ldw, void *stream) {
+int ss_linear_bf16_dx_det(const void *x, const void *w, const void *mul, void *y, float *colsum, int32_t M, int32_t N, int32_t K, int32_t ldy, void *workspace,
+                          int64_t workspace_bytes, void *stream) {
+  if (!mul || !y || !colsum) return fail(SS_ERR_INVALID, "null argument");
+  return linear_train_impl(x, w, nullptr, mul, y, nullptr, nullptr, M, N, K, ldy, 0, SS_ACT_NONE, 0, colsum, stream, true, workspace, workspace_bytes);
+}
+
+int64_t ss_linear_bf16_dx_det_workspace(int32_t M, int32_t N, int32_t K) {
+  if (M < 1 || N < 1 || K < 64 || K % 64 || !dx_served(M, N, K)) {
+    fail(SS_ERR_INVALID, "ss_linear_bf16_dx_det_workspace: M >= 2048, N >= 256, K a multiple of 128 (the shapes ss_linear_bf16_dx serves)");
+    return -1;
+  }
+  return (int64_t)2 * ((M + 255) / 256) * N * 4;
+}
+
+static int wgrad_impl(const void *dz, const void *h, float *dw, int32_t Mb, int32_t n_out, int32_t n_in, int32_t ldz, int32_t ldh, int32_t ldw, void *stream, bool det,
+                      void *workspace, int64_t workspace_bytes) {
   if (!dz || !h || !dw) return fail(SS_ERR_INVALID, "null argument");
   if (Mb < 128 || Mb % 128 || n_out < 1 || n_in < 1 || ldz < n_out || ldh < n_in || ldw < n_in || (ldz & 7) || (ldh & 7) || (n_out & 7) || (n_in & 7) ||
       (reinterpret_cast<size_t>(dz) & 15) || (reinterpret_cast<size_t>(h) & 15))
@@ -1053,9 +1151,36 @@ int ss_wgrad_bf16(const void *dz, const void *h, float *dw, int32_t Mb, int32_t 
   split_256(p, (long long)gx * gy, nkt);
   p.grid = dim3(gx, gy, p.ksplit);
   p.lds = gemm256::LoopTN::LDS_BYTES;
-  WgradArgs a{static_cast<const __bf16 *>(dz), static_cast<const __bf16 *>(h), dw, n_out, n_in, ldz, ldh, ldw, nkt, p.kper};
+  p.det = det;
+  if (det) {
+    if ((long long)n_out * n_in > (1ll << 30)) return fail(SS_ERR_INVALID, "ss_wgrad_bf16_det: more than 2^30 outputs");
+    if (check_workspace(workspace, workspace_bytes, (int64_t)p.ksplit * n_out * n_in * 4) != SS_OK) return SS_ERR_INVALID;
+  }
+  // the deterministic form: the shares' images dense in the workspace (row stride n_in), then one fixed-order pass adds them to dw
+  WgradArgs a{static_cast<const __bf16 *>(dz), static_cast<const __bf16 *>(h), det ? static_cast<float *>(workspace) : dw, n_out, n_in, ldz, ldh, det ? n_in : ldw, nkt, p.kper};
   void *args[] = {&a};
-  return launch_gemm(p, args, (hipStream_t)stream);
+  const int rc = launch_gemm(p, args, (hipStream_t)stream);
+  if (rc != SS_OK || !det) return rc;
+  return launch_reduce(a.dW, dw, n_out, n_in, ldw, p.ksplit, (hipStream_t)stream);
+}
+
+int ss_wgrad_bf16(const void *dz, const void *h, float *dw, int32_t Mb, int32_t n_out, int32_t n_in, int32_t ldz, int32_t ldh, int32_t ldw, void *stream) {
+  return wgrad_impl(dz, h, dw, Mb, n_out, n_in, ldz, ldh, ldw, stream, false, nullptr, 0);
+}
+
+int ss_wgrad_bf16_det(const void *dz, const void *h, float *dw, int32_t Mb, int32_t n_out, int32_t n_in, int32_t ldz, int32_t ldh, int32_t ldw, void *workspace,
+                      int64_t workspace_bytes, void *stream) {
+  return wgrad_impl(dz, h, dw, Mb, n_out, n_in, ldz, ldh, ldw, stream, true, workspace, workspace_bytes);
+}
+
+int64_t ss_wgrad_bf16_det_workspace(int32_t Mb, int32_t n_out, int32_t n_in) {
+  if (Mb < 128 || Mb % 128 || n_out < 1 || n_in < 1 || (n_out & 7) || (n_in & 7) || (long long)n_out * n_in > (1ll << 30)) {
+    fail(SS_ERR_INVALID, "ss_wgrad_bf16_det_workspace: the batch a multiple of 128 rows; n_out, n_in multiples of 8");
+    return -1;
+  }
+  GemmPlan p{GEMM_WGRAD, true};
+  split_256(p, (long long)((n_in + 255) / 256) * ((n_out + 255) / 256), Mb / 64);
+  return (int64_t)p.ksplit * n_out * n_in * 4;
 }
 
 int ss_debug_last_gemm(char *buf, int32_t len) {

@@ -15,6 +15,11 @@ No transposed copies of activations or gradients exist: the forward and dX produ
 the first version of this file wrote h^T and dZ^T next to h and dZ so that the weight gradient could be the K-contiguous `x W^T` kernel — 1.35 of the 3.4 GB a
 pass wrote.  bf16 operands, fp32 accumulation: the precision class of the autocast path it replaces (weights, activations and gradients of activations rounded
 to bf16; weight gradients and the head's output fp32).  No CPU path: the package has none.
+
+deterministic=True: the default backward pass is not reproducible from run to run — the batch split of every weight gradient and the per-wave column sums
+meet in their outputs by fp32 atomics, in the order the workgroups finish.  The deterministic pass calls ss_wgrad_bf16_det / ss_linear_bf16_dx_det instead:
+the same products, their partial sums stored into one workspace (the largest request of the pass, ~67 MB at the production widths) and added in a fixed order
+by a second launch, each reduce finishing in stream order before the next product writes its partials.
 """
 import torch
 
@@ -59,7 +64,7 @@ class _FusedMLP(torch.autograd.Function):
     """y = Linear_{L+1}(act(Linear_L(... act(Linear_1(x))))) with x [M, D] fp32; params = W_1, b_1, ..., W_{L+1}, b_{L+1} (fp32, torch.nn.Linear layout)."""
 
     @staticmethod
-    def forward(ctx, x, act, bufs, track, *params):
+    def forward(ctx, x, act, bufs, track, det, *params):
         dev, st = x.device, _launch_stream(x.device)
         ws, bs = params[0::2], params[1::2]
         nl = len(ws)
@@ -96,6 +101,7 @@ class _FusedMLP(torch.autograd.Function):
         _check(lib().ss_linear_bf16(_ptr(h), _ptr(wb), _ptr(bs[-1].detach().float().contiguous()), _ptr(out), Mp, w.shape[0], kpad[-1], w.shape[0],
                                     _cabi.ACTIVATIONS["none"], 1, st))
         ctx.act, ctx.M, ctx.Mp, ctx.kpad, ctx.dims = act, M, Mp, kpad, [(w_.shape[0], w_.shape[1]) for w_ in ws]
+        ctx.det = det
         ctx.hs, ctx.gs, ctx.wbs = hs, gs, wbs
         return out[:M]
 
@@ -118,11 +124,23 @@ class _FusedMLP(torch.autograd.Function):
         # [53 248, 69] tensor took 180 us, a matrix-vector product through rocBLAS 175)
         ones = bufs.get("ones", (Mp, 8), bf, dev, fresh, lambda t: t[:, 0].fill_(1.0))
         dbh = torch.zeros(_pad(nh, 8), 8, dtype=torch.float32, device=dev)
-        _check(lib().ss_wgrad_bf16(_ptr(dz), _ptr(ones), _ptr(dbh), Mp, _pad(nh, 8), 8, nhp, 8, 8, st))
+        no8s = [_pad(d[0], 8) for d in dims]
+        # dX products the 256 x 256 kernel serves (column sums from the same launch); the others leave the bias gradient to torch
+        dx256 = [i > 0 and Mp >= 2048 and kpad[i] >= 256 and (nhp if i == nl - 1 else dims[i][0]) % 128 == 0 for i in range(nl)]
+        L = lib()
+        if ctx.det:
+            # one workspace for every product of the pass, the largest request; reused in stream order (a reduce ends before the next product starts)
+            need = [L.ss_wgrad_bf16_det_workspace(Mp, no8s[-1], 8)] + [L.ss_wgrad_bf16_det_workspace(Mp, no8s[i], kpad[i]) for i in range(nl)]
+            need += [L.ss_linear_bf16_dx_det_workspace(Mp, kpad[i], nhp if i == nl - 1 else dims[i][0]) for i in range(1, nl) if dx256[i]]
+            assert min(need) > 0, need
+            wsp = bufs.get("det_ws", (max(need) // 4,), torch.float32, dev, fresh)
+            wgrad, dx, tail = L.ss_wgrad_bf16_det, L.ss_linear_bf16_dx_det, (_ptr(wsp), wsp.numel() * 4, st)
+        else:
+            wgrad, dx, tail = L.ss_wgrad_bf16, L.ss_linear_bf16_dx, (st,)
+        _check(wgrad(_ptr(dz), _ptr(ones), _ptr(dbh), Mp, no8s[-1], 8, nhp, 8, 8, *tail))
         db = dbh[:nh, 0]
         # every weight and bias gradient of the pass in ONE zero-filled tensor (the kernels accumulate into them: 13 memsets otherwise).  Not kept between
         # passes: the optimiser holds the views as .grad until the next backward
-        no8s = [_pad(d[0], 8) for d in dims]
         sizes = [no8s[i] * kpad[i] for i in range(nl)] + [kpad[i] for i in range(1, nl)]
         offs = [0]
         for z in sizes:
@@ -137,7 +155,7 @@ class _FusedMLP(torch.autograd.Function):
             # dW [n_out, kpad_i] = dZ^T h_below with both operands as they lie (ss_wgrad_bf16 contracts over their rows); db = the column sums of dZ
             no8 = no8s[i]
             dw = flat[offs[i]:offs[i] + no8 * kpad[i]].view(no8, kpad[i])
-            _check(lib().ss_wgrad_bf16(_ptr(dz), _ptr(ctx.hs[i]), _ptr(dw), Mp, no8, kpad[i], n_outp, kpad[i], kpad[i], st))
+            _check(wgrad(_ptr(dz), _ptr(ctx.hs[i]), _ptr(dw), Mp, no8, kpad[i], n_outp, kpad[i], kpad[i], *tail))
             grads[2 * i] = dw[:n_out, :n_in]
             grads[2 * i + 1] = db if db is not None else dz[:, :n_out].sum(0, dtype=torch.float32)
             if i > 0:
@@ -146,9 +164,9 @@ class _FusedMLP(torch.autograd.Function):
                 wt = wts[i]
                 nb = kpad[i]
                 dzb = bufs.get(("dz", i), (Mp, nb), bf, dev, fresh)
-                if Mp >= 2048 and nb >= 256 and n_outp % 128 == 0:
+                if dx256[i]:
                     db = flat[offs[nl + i - 1]:offs[nl + i - 1] + nb]
-                    _check(lib().ss_linear_bf16_dx(_ptr(dz), _ptr(wt), _ptr(ctx.gs[i - 1]), _ptr(dzb), _ptr(db), Mp, nb, n_outp, nb, st))
+                    _check(dx(_ptr(dz), _ptr(wt), _ptr(ctx.gs[i - 1]), _ptr(dzb), _ptr(db), Mp, nb, n_outp, nb, *tail))
                 else:
                     db = None
                     _linear_train(dz, wt, None, ctx.gs[i - 1], dzb, None, None, Mp, nb, n_outp, nb, 0, none, False, st)
@@ -156,14 +174,14 @@ class _FusedMLP(torch.autograd.Function):
         ctx.hs = ctx.gs = ctx.wbs = None
         if ctx.bufs is not None:
             ctx.bufs.busy = False
-        return (None, None, None, None, *grads)
+        return (None, None, None, None, None, *grads)
 
 
 class FusedMLPTrain:
     """Callable over an existing stack of torch.nn.Linear layers (the hidden ones followed by `act`, then the head): differentiable with
     respect to the layers' parameters, not to the input (the update's inputs are rollout states)."""
 
-    def __init__(self, hidden_layers, head, activation_name):
+    def __init__(self, hidden_layers, head, activation_name, deterministic=False):
         if activation_name not in _cabi.ACTIVATIONS or activation_name == "none":
             raise ValueError(f"activation {activation_name!r} has no fused epilogue (silu, tanh, relu)")
         self.layers = list(hidden_layers) + [head]
@@ -171,6 +189,7 @@ class FusedMLPTrain:
         dev = self.layers[0].weight.device
         if dev.type != "cuda":
             raise RuntimeError("FusedMLPTrain needs the networks on a GPU (there is no CPU path)")
+        self.deterministic = bool(deterministic)                  # the backward pass's reductions in a fixed order (module docstring)
         self.bufs, self.bufs_nograd = _Buffers(), _Buffers()
 
     def __call__(self, x):
@@ -178,4 +197,4 @@ class FusedMLPTrain:
         for l in self.layers:
             params += [l.weight, l.bias]
         track = torch.is_grad_enabled()                           # (inside Function.forward the grad mode is always off)
-        return _FusedMLP.apply(x.detach().float(), self.act, self.bufs if track else self.bufs_nograd, track, *params)
+        return _FusedMLP.apply(x.detach().float(), self.act, self.bufs if track else self.bufs_nograd, track, self.deterministic, *params)
