@@ -6,7 +6,7 @@
  * GEMM-shaped (4096 x 289 -> 2048 -> 1536 -> 1024 -> 1024 -> 512 -> 512 -> 69: 59 GFLOP per env step) and sits in the
  * sampling loop next to ss_step, so it runs on the matrix cores: bf16 operands, fp32 accumulation
  * (v_mfma_f32_32x32x16_bf16), bias + activation fused into the GEMM's epilogue, activations kept in bf16 between layers.
- * The PPO update (backward pass) stays with the caller's autograd framework.
+ * The PPO update's products and loss heads follow below; the optimiser and the chain rule between them stay with the caller.
  *
  * Conventions as in smplsim_hip.h: device pointers, int status + ss_last_error(), work enqueued on the caller's stream.
  */
@@ -93,6 +93,52 @@ int64_t ss_wgrad_bf16_det_workspace(int32_t Mb, int32_t n_out, int32_t n_in);
  * mean, noise [M, dim] dense f32; log_std [dim].  The caller draws the noise (its generator, its stream order). */
 int ss_gaussian_sample(const float *mean, const float *noise, const float *log_std, int32_t M, int32_t dim, float *action, int32_t lda,
                        float *action_env, int32_t lde, float clip_lo, float clip_hi, float *logp, void *stream);
+
+/* The PPO update's loss heads (the step between the networks' forward passes and their backward products; they replace ~15 elementwise and reduction launches
+ * forward and as many through autograd in the reference's update_policy / update_value, agents/agent_ppo.py:20-83).  For a caller without autograd they give the
+ * head's dZ that ss_wgrad_bf16 / ss_linear_bf16_dx start from.
+ *
+ * Both heads are reproducible and have no second variant: every output is a function of the arguments and the input bytes alone — not of the order in which
+ * workgroups run, nor of what the workspace held before.  No atomics.  Every per-element and per-row value is formed in fp64 from the fp32 inputs and rounded to
+ * fp32 once, when it is stored; every sum is an fp64 sum in the order stated below, rounded to fp32 once at the end.  Two launches each on `stream` (the head, the
+ * reduce); the workspace is caller-owned, 16-byte aligned, and may be reused by the next call on the same stream.  SS_ERR_INVALID, nothing launched: a null required
+ * pointer, M < 1, a row stride below the row's width, a null, misaligned or too-small workspace, a bf16 gradient whose ldd is not a multiple of 8 or whose base is
+ * not 16-byte aligned (what ss_wgrad_bf16 asks of its operands).  The workspace queries return a negative value (and set ss_last_error) for invalid shapes.
+ *
+ * ss_ppo_policy_head: the clipped surrogate of AgentPPO.ppo_loss over PolicyGaussian.get_log_prob.  mean [M, ldm], actions [M, lda] f32; log_std [dim], adv [M],
+ * old_logp [M] f32; 1 <= dim <= 256 (a wavefront keeps a row's columns in registers, four trips of 64), clip_eps in (0, 1).  Per row i, with lo = 1 - clip_eps and
+ * hi = 1 + clip_eps, both formed in fp64 from the float argument (for clip_eps = 0.2f: 0.799999997 and 1.200000003, where an fp32 evaluation clamps at
+ * float(0.8) = 0.80000001 and float(1.2); clip_frac's "r_i outside [lo, hi]" is |r_i - 1| > clip_eps with that clip_eps):
+ *   z_ij   = (a_ij - mean_ij) * exp(-log_std_j)
+ *   logp_i = sum_j (-z_ij^2 / 2 - log_std_j - log sqrt(2 pi))
+ *   r_i    = exp(logp_i - old_logp_i);  s1 = r_i A_i;  s2 = clamp(r_i, lo, hi) A_i   (a NaN stays a NaN through the clamp and the minimum, as in torch)
+ *   g_i    = -(1 / M) r_i (s1 <= s2 ? A_i : 0)                     (dloss / dlogp_i: what autograd gives for -minimum(s1, s2).mean(), ties and a ratio on a bound included)
+ * outputs
+ *   logp     [M] f32 or NULL
+ *   dmean    [M, ldd] f32 (dmean_is_bf16 = 0) or bf16 (the round-to-nearest-even of the f32 value):  g_i z_ij exp(-log_std_j).  Rows >= M and columns >= dim are not written.
+ *   dlog_std [dim] f32 or NULL, overwritten:  sum_i g_i (z_ij^2 - 1)
+ *   stats    [4] f32, overwritten:  loss = -(1 / M) sum_i min(s1, s2);  clip_frac = (1 / M) #{i: r_i < lo or r_i > hi};  approx_kl = (1 / M) sum_i (old_logp_i - logp_i);
+ *            mean_ratio = (1 / M) sum_i r_i
+ * A NaN in one row's mean gives a NaN loss and NaN in that row of dmean (and in dlog_std); the other rows of dmean are not affected.
+ *   workspace  at least ss_ppo_policy_head_workspace(M, dim) = ceil(M / 128) * (4 + dim) * 8 bytes.  After the call it holds P = ceil(M / 128) rows of 4 + dim doubles, dense:
+ *              row p is the sum over the rows [128 p, min(128 p + 128, M)) of  min(s1, s2) | (r_i outside [lo, hi]) | old_logp_i - logp_i | r_i | g_i (z_ij^2 - 1), j = 0 .. dim - 1.
+ *   order      a row's logp: lane l of the row's wavefront adds its columns l, l + 64, ... ascending, then the 64 lanes meet by the xor butterfly (distances 32, 16, 8, 4, 2, 1).
+ *              A partial row: wavefront w of workgroup p adds its rows 128 p + 32 w .. 128 p + 32 w + 31 ascending, then ((w_0 + w_1) + w_2) + w_3.
+ *              The reduce: (((P_0 + P_1) + P_2) + ... + P_{P-1}) per column, ascending from row 0; the first four columns divided by M (the first negated) are stats. */
+int ss_ppo_policy_head(const float *mean, int32_t ldm, const float *actions, int32_t lda, const float *log_std, const float *adv, const float *old_logp, int32_t M,
+                       int32_t dim, float clip_eps, float *logp, void *dmean, int32_t ldd, int32_t dmean_is_bf16, float *dlog_std, float *stats, void *workspace,
+                       int64_t workspace_bytes, void *stream);
+int64_t ss_ppo_policy_head_workspace(int32_t M, int32_t dim);
+
+/* ss_value_head: the critic's loss of AgentPPO.update_value.  pred, target [M] f32 (dense).
+ *   dpred [M, ldd] f32 or bf16 (dpred_is_bf16; one column, ldd >= 1):  2 (pred_i - target_i) / M          loss [1] f32, overwritten:  (1 / M) sum_i (pred_i - target_i)^2
+ * A NaN in pred gives a NaN loss and a NaN in that row of dpred only.
+ *   workspace  at least ss_value_head_workspace(M) = ceil(M / 1024) * 8 bytes: P = ceil(M / 1024) doubles, partial p the sum of the squares over the rows [1024 p, min(1024 p + 1024, M)).
+ *   order      thread t of workgroup p adds its rows 1024 p + t + 256 k, k = 0 .. 3 ascending; a wavefront's 64 lanes meet by the xor butterfly (32 .. 1); the
+ *              four wavefronts ((w_0 + w_1) + w_2) + w_3; the reduce adds the partials ascending from p = 0, then divides by M. */
+int ss_value_head(const float *pred, const float *target, int32_t M, void *dpred, int32_t ldd, int32_t dpred_is_bf16, float *loss, void *workspace,
+                  int64_t workspace_bytes, void *stream);
+int64_t ss_value_head_workspace(int32_t M);
 
 /* Test hook: the GEMM instantiation launched last by an ss_linear_* / ss_wgrad_bf16* call on the calling host thread, as
  * "<family> mode=<G256 mode or -> bn=<BN> bk=<BK> waves=<waves per workgroup> out=<bf16|f32|f32acc|f32det> ksplit=<K shares> kper=<K tiles per share>"

@@ -143,7 +143,8 @@ def bind(lib):
 FIELDS = {"qpos": 0, "qvel": 1, "xpos": 2, "xmat": 3, "body_vel": 4, "touch": 5, "qacc_warm": 6, "cur_t": 7}   # SS_FIELD_*
 ACTIVATIONS = {"none": 0, "silu": 1, "tanh": 2, "relu": 3}
 MLP_EXPORTS = ["ss_linear_bf16", "ss_linear_bf16_train", "ss_linear_bf16_dx", "ss_wgrad_bf16", "ss_obs_to_bf16", "ss_gaussian_sample",
-               "ss_debug_last_gemm", "ss_linear_bf16_dx_det", "ss_linear_bf16_dx_det_workspace", "ss_wgrad_bf16_det", "ss_wgrad_bf16_det_workspace"]            # include/smplsim_mlp.h (product library only: the matrix-core kernels)
+               "ss_debug_last_gemm", "ss_linear_bf16_dx_det", "ss_linear_bf16_dx_det_workspace", "ss_wgrad_bf16_det", "ss_wgrad_bf16_det_workspace",
+               "ss_ppo_policy_head", "ss_ppo_policy_head_workspace", "ss_value_head", "ss_value_head_workspace"]            # include/smplsim_mlp.h (product library only: the matrix-core kernels)
 
 
 def bind_mlp(lib):
@@ -159,6 +160,12 @@ def bind_mlp(lib):
     lib.ss_obs_to_bf16.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_float, C.c_float, C.c_float, vp, C.c_int32, vp]
     lib.ss_gaussian_sample.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_float, C.c_float, vp, vp]
     lib.ss_debug_last_gemm.argtypes = [C.c_char_p, C.c_int32]
+    # (mean, ldm, actions, lda, log_std, adv, old_logp, M, dim, clip_eps, logp, dmean, ldd, dmean_is_bf16, dlog_std, stats, workspace, bytes, stream)
+    lib.ss_ppo_policy_head.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int64, vp]
+    lib.ss_ppo_policy_head_workspace.argtypes = [C.c_int32, C.c_int32]; lib.ss_ppo_policy_head_workspace.restype = C.c_int64
+    # (pred, target, M, dpred, ldd, dpred_is_bf16, loss, workspace, bytes, stream)
+    lib.ss_value_head.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, C.c_int64, vp]
+    lib.ss_value_head_workspace.argtypes = [C.c_int32]; lib.ss_value_head_workspace.restype = C.c_int64
     return lib
 
 

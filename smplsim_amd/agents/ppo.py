@@ -48,6 +48,7 @@ class PPOConfig:
     mfma_inference: bool = False   # sampler: policy forward by the library's fused bf16 MFMA kernels (learning/fast_policy.py)
     mfma_update: bool = False      # update: the networks' forward AND backward passes on the library's own GEMM (learning/fused_train.py), bf16 operands
     deterministic_update: bool = False   # with mfma_update: the update's reductions in a fixed order (same seed, same bits; DESIGN.md "deterministic update")
+    fused_loss: bool = False       # update: surrogate, value loss and their gradients by the library's loss heads (learning/fused_loss.py), whichever path ran the networks
     extra: dict = field(default_factory=dict)
 
 
@@ -58,6 +59,8 @@ class AgentPPO:
         self.device = env.device
         if c.deterministic_update and not c.mfma_update:
             raise ValueError("deterministic_update applies to the mfma_update path only (the torch update paths are reproducible as they are)")
+        if c.fused_loss and self.device.type != "cuda":
+            raise RuntimeError("fused_loss needs the env on a GPU (the loss heads have no CPU path)")
         torch.manual_seed(seed)
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed)
@@ -80,6 +83,10 @@ class AgentPPO:
             from ..learning.fused_train import FusedMLPTrain
             self.fused_policy = FusedMLPTrain(self.policy_net.net.affine_layers, self.policy_net.action_mean, c.activation, deterministic=c.deterministic_update)
             self.fused_value = FusedMLPTrain(self.value_net.net.affine_layers, self.value_net.value_head, c.activation, deterministic=c.deterministic_update)
+        self.surrogate = self.value_mse = None
+        if c.fused_loss:
+            from ..learning.fused_loss import PPOSurrogate, ValueMSE
+            self.surrogate, self.value_mse = PPOSurrogate(), ValueMSE()
 
     # ------------------------------------------------------------------ sampling
     def _prep_obs(self, obs):
@@ -217,6 +224,15 @@ class AgentPPO:
         return torch.matmul(terms, torch.ones(terms.shape[1], 1, dtype=terms.dtype, device=terms.device))
 
     def ppo_loss(self, states, actions, advantages, fixed_log_probs):
+        if getattr(self, "surrogate", None) is not None:
+            # fused_loss: the head's fp32 mean from whichever path runs the network; log-density, surrogate and both gradients in ss_ppo_policy_head
+            p = self.policy_net
+            if self.fused_policy is not None:
+                mean = self.fused_policy(p.norm(states))
+            else:
+                with self._autocast():
+                    mean = self._f32(p.mean_and_log_std(states)[0])
+            return self.surrogate(mean, p.action_log_std, actions, advantages, fixed_log_probs, self.cfg.clip_epsilon)
         if getattr(self, "fused_policy", None) is not None:
             log_probs = self._policy_log_prob(states, actions)
         else:
@@ -233,7 +249,7 @@ class AgentPPO:
             else:
                 with self._autocast():
                     pred = self._f32(self.value_net(critic_states))
-            loss = (pred - returns).pow(2).mean()
+            loss = self.value_mse(pred, returns) if getattr(self, "value_mse", None) is not None else (pred - returns).pow(2).mean()
             self.optimizer_value.zero_grad(set_to_none=True)
             loss.backward()
             self.optimizer_value.step()
@@ -272,6 +288,9 @@ class AgentPPO:
                 torch.nn.utils.clip_grad_norm_(self.policy_net.parameters(), c.policy_grad_clip)
             self.optimizer_policy.step()
             info["surr_loss"] = loss.detach()
+        stats = getattr(getattr(self, "surrogate", None), "last_stats", None)
+        if stats is not None:
+            info["clip_frac"], info["approx_kl"] = stats[1], stats[2]   # of the last iteration, from the head's launch
         if self.fast_policy is not None:
             self.fast_policy.refresh()                          # bf16 snapshots of the updated weights for the sampler
         self.epoch += 1

@@ -26,6 +26,7 @@
 #include "../../include/smplsim_mlp.h"
 #include "ss_api.h"
 #include "ss_gemm256.h"
+#include "ss_ppo_head.h"
 
 namespace {
 
@@ -1206,6 +1207,65 @@ int ss_obs_to_bf16(const float *obs, int32_t M, int32_t dim, int32_t obs_stride,
   const long long total = (long long)M * kpad;
   hipLaunchKernelGGL(ss_obs_to_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, obs, M, dim, obs_stride, mean, sd,
                      reinterpret_cast<const long long *>(n), lo, hi, clip, static_cast<__bf16 *>(out), kpad);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
+}
+
+// ---- the PPO loss heads (ss_ppo_head.h): two launches each on `stream`, the heads' partial rows into the caller's workspace, then the fixed-order reduce
+static int64_t row_groups(int32_t M, int rows) { return ((int64_t)M + rows - 1) / rows; }             // in 64 bits: M + rows - 1 may pass INT32_MAX
+static int64_t policy_head_bytes(int32_t M, int32_t dim) { return row_groups(M, ppo_head::POLICY_ROWS) * (ppo_head::NSTATS + dim) * 8; }
+static int64_t value_head_bytes(int32_t M) { return row_groups(M, ppo_head::VALUE_ROWS) * 8; }
+static bool bad_bf16_grad(const void *g, int32_t ldd) { return (ldd & 7) || (reinterpret_cast<size_t>(g) & 15); }
+
+int64_t ss_ppo_policy_head_workspace(int32_t M, int32_t dim) {
+  if (M < 1 || dim < 1 || dim > ppo_head::MAX_DIM) {
+    fail(SS_ERR_INVALID, "ss_ppo_policy_head_workspace: M >= 1, 1 <= dim <= 256");
+    return -1;
+  }
+  return policy_head_bytes(M, dim);
+}
+
+int ss_ppo_policy_head(const float *mean, int32_t ldm, const float *actions, int32_t lda, const float *log_std, const float *adv, const float *old_logp, int32_t M,
+                       int32_t dim, float clip_eps, float *logp, void *dmean, int32_t ldd, int32_t dmean_is_bf16, float *dlog_std, float *stats, void *workspace,
+                       int64_t workspace_bytes, void *stream) {
+  if (!mean || !actions || !log_std || !adv || !old_logp || !dmean || !stats) return fail(SS_ERR_INVALID, "null argument");
+  if (M < 1 || dim < 1 || dim > ppo_head::MAX_DIM) return fail(SS_ERR_INVALID, "ss_ppo_policy_head: M >= 1, 1 <= dim <= 256");
+  if (ldm < dim || lda < dim || ldd < dim) return fail(SS_ERR_INVALID, "ss_ppo_policy_head: row strides must be >= dim");
+  if (!(clip_eps > 0.f && clip_eps < 1.f)) return fail(SS_ERR_INVALID, "ss_ppo_policy_head: clip_eps must lie in (0, 1)");
+  if (dmean_is_bf16 && bad_bf16_grad(dmean, ldd)) return fail(SS_ERR_INVALID, "ss_ppo_policy_head: a bf16 dmean needs ldd a multiple of 8 and a 16-byte aligned base");
+  if (check_workspace(workspace, workspace_bytes, policy_head_bytes(M, dim)) != SS_OK) return SS_ERR_INVALID;
+  const int P = (int)row_groups(M, ppo_head::POLICY_ROWS), W = ppo_head::NSTATS + dim;
+  const ppo_head::PolicyHeadArgs a{mean, actions, log_std, adv, old_logp, logp, dmean, static_cast<double *>(workspace), M, dim, ldm, lda, ldd,
+                                   1.0 - (double)clip_eps, 1.0 + (double)clip_eps, 1.0 / M};
+  hipStream_t st = (hipStream_t)stream;
+  if (dmean_is_bf16) hipLaunchKernelGGL(ppo_head::ss_ppo_policy_head_kernel<true>, dim3((unsigned)P), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(ppo_head::ss_ppo_policy_head_kernel<false>, dim3((unsigned)P), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(ppo_head::ss_head_reduce_kernel, dim3((unsigned)((W + 63) / 64)), dim3(64), 0, st, a.part, P, W, stats, ppo_head::NSTATS, dlog_std, (double)M, -1.0);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
+}
+
+int64_t ss_value_head_workspace(int32_t M) {
+  if (M < 1) {
+    fail(SS_ERR_INVALID, "ss_value_head_workspace: M >= 1");
+    return -1;
+  }
+  return value_head_bytes(M);
+}
+
+int ss_value_head(const float *pred, const float *target, int32_t M, void *dpred, int32_t ldd, int32_t dpred_is_bf16, float *loss, void *workspace,
+                  int64_t workspace_bytes, void *stream) {
+  if (!pred || !target || !dpred || !loss) return fail(SS_ERR_INVALID, "null argument");
+  if (M < 1) return fail(SS_ERR_INVALID, "ss_value_head: M >= 1");
+  if (ldd < 1) return fail(SS_ERR_INVALID, "ss_value_head: row strides must be >= 1");
+  if (dpred_is_bf16 && bad_bf16_grad(dpred, ldd)) return fail(SS_ERR_INVALID, "ss_value_head: a bf16 dpred needs ldd a multiple of 8 and a 16-byte aligned base");
+  if (check_workspace(workspace, workspace_bytes, value_head_bytes(M)) != SS_OK) return SS_ERR_INVALID;
+  const int P = (int)row_groups(M, ppo_head::VALUE_ROWS);
+  double *part = static_cast<double *>(workspace);
+  hipStream_t st = (hipStream_t)stream;
+  if (dpred_is_bf16) hipLaunchKernelGGL(ppo_head::ss_value_head_kernel<true>, dim3((unsigned)P), dim3(256), 0, st, pred, target, M, dpred, ldd, part, 1.0 / M);
+  else hipLaunchKernelGGL(ppo_head::ss_value_head_kernel<false>, dim3((unsigned)P), dim3(256), 0, st, pred, target, M, dpred, ldd, part, 1.0 / M);
+  hipLaunchKernelGGL(ppo_head::ss_head_reduce_kernel, dim3(1), dim3(64), 0, st, part, P, 1, loss, 1, static_cast<float *>(nullptr), (double)M, 1.0);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
 }
