@@ -6,7 +6,7 @@
  * GEMM-shaped (4096 x 289 -> 2048 -> 1536 -> 1024 -> 1024 -> 512 -> 512 -> 69: 59 GFLOP per env step) and sits in the
  * sampling loop next to ss_step, so it runs on the matrix cores: bf16 operands, fp32 accumulation
  * (v_mfma_f32_32x32x16_bf16), bias + activation fused into the GEMM's epilogue, activations kept in bf16 between layers.
- * The PPO update's products and loss heads follow below; the optimiser and the chain rule between them stay with the caller.
+ * The PPO update's products, loss heads and optimiser step (ss_adam_step) follow below; the chain rule between them stays with the caller.
  *
  * Conventions as in smplsim_hip.h: device pointers, int status + ss_last_error(), work enqueued on the caller's stream.
  */
@@ -139,6 +139,48 @@ int64_t ss_ppo_policy_head_workspace(int32_t M, int32_t dim);
 int ss_value_head(const float *pred, const float *target, int32_t M, void *dpred, int32_t ldd, int32_t dpred_is_bf16, float *loss, void *workspace,
                   int64_t workspace_bytes, void *stream);
 int64_t ss_value_head_workspace(int32_t M);
+
+/* ss_adam_step: the optimiser step of the update for all tensors of a network in one call — the global gradient norm, clip_grad_norm_'s coefficient, Adam, and the
+ * bf16 images of the new weights that the next network pass reads (W for the forward products, W^T for ss_linear_bf16_dx).  It is torch.optim.Adam with
+ * amsgrad = False, maximize = False (the reference's optimiser, agents/agent_ppo.py:85-88) preceded by torch.nn.utils.clip_grad_norm_(..., error_if_nonfinite = False)
+ * (policy_grad_clip, agent_humanoid.py:110-111).  Reproducible like the loss heads: no atomics, every output a function of the arguments and the input bytes alone;
+ * every value is formed in fp64 from the fp32 inputs and rounded to fp32 once, when it is stored:
+ *   S      = sum over all tensors and elements of g^2            (fixed order, below)
+ *   norm   = sqrt(S);  c = min(1, max_grad_norm / (norm + 1e-6))   (clip_grad_norm_'s coefficient; 1 when clipping is off)
+ *   g'     = c g + weight_decay p
+ *   m'     = beta1 m + (1 - beta1) g'
+ *   v'     = beta2 v + (1 - beta2) g'^2
+ *   p'     = p - (lr / (1 - beta1^step)) m' / (sqrt(v') / sqrt(1 - beta2^step) + eps)
+ * A NaN or Inf anywhere in the gradients gives a non-finite norm, and through c it reaches every parameter of the call (as in torch; with clipping off only the
+ * elements it touches).
+ *   tensors   a HOST array of `count` descriptors, 1 <= count <= 32 (SS_ERR_INVALID beyond); it is copied into the kernel arguments and may be freed on return.
+ *             p, m, v   fp32 [rows, cols] dense: parameter, exp_avg, exp_avg_sq; overwritten with p', m', v'.
+ *             g         fp32 [rows, cols], row stride ldg >= cols, unit column stride; not modified.
+ *             w_bf16    [rows, ld_w] bf16 or NULL: the round-to-nearest-even bf16 of the STORED fp32 p' (a NaN as 0x7FC0).  ld_w >= cols, a multiple of 8, the base
+ *                       16-byte aligned; columns >= cols are not written (the owner zeroes them once).
+ *             wt_bf16   [cols, ld_wt] bf16 or NULL: the same values transposed.  ld_wt >= rows, a multiple of 8, the base 16-byte aligned; elements outside
+ *                       [cols, rows] are not written.
+ *   step      >= 1, the number of this step (kept on the host, as torch.optim.Adam does by default); betas in [0, 1), eps >= 0.
+ *   max_grad_norm   <= 0 or +inf: no clipping (the norm is still formed and reported).     grad_norm  [1] f32 on the device or NULL: float(norm).
+ *   workspace caller-owned, 16-byte aligned, at least ss_adam_step_workspace(tensors, count) = (T + 1) * 8 bytes, T the number of tiles of the call: every tensor is cut
+ *             into tiles of 64 rows x 64 columns, numbered in descriptor order and row-major within a tensor.  After the call workspace[tile] is the tile's fp64 sum of
+ *             squares and workspace[T] is S.
+ *   order     a tile: thread t of its 256-thread workgroup owns the rows (t >> 4) + 16 k, k = 0 .. 3, and in each the columns 4 (t & 15) .. 4 (t & 15) + 3; it adds its
+ *             squares with k ascending, the columns ascending within a row; a wavefront's 64 lanes meet by the xor butterfly (32, 16, ..., 1); the four wavefronts
+ *             ((w0 + w1) + w2) + w3.  S: the tiles' partials ascending from tile 0, by one wavefront.
+ * Three launches on `stream` (partials, reduce, step), no host synchronisation, nothing read back.  Whole tiles of a tensor with cols a multiple of 4 (p, m, v 16-byte
+ * aligned) are updated by 16-byte accesses and their part of wt_bf16 is written as 16-byte row segments through an LDS transpose; edge tiles and other tensors go
+ * element by element.  SS_ERR_INVALID, nothing launched: the checks of the heads' style (null required pointers, rows / cols < 1, strides below the width, the
+ * images' alignment, count, step, betas, eps, the workspace).  The query returns a negative value (and sets ss_last_error) for invalid descriptors. */
+typedef struct ss_adam_tensor {
+  float *p, *m, *v;
+  const float *g;
+  void *w_bf16, *wt_bf16;
+  int32_t rows, cols, ldg, ld_w, ld_wt;
+} ss_adam_tensor;
+int ss_adam_step(const ss_adam_tensor *tensors, int32_t count, int32_t step, double lr, double beta1, double beta2, double eps, double weight_decay,
+                 double max_grad_norm, float *grad_norm, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t ss_adam_step_workspace(const ss_adam_tensor *tensors, int32_t count);
 
 /* Test hook: the GEMM instantiation launched last by an ss_linear_* / ss_wgrad_bf16* call on the calling host thread, as
  * "<family> mode=<G256 mode or -> bn=<BN> bk=<BK> waves=<waves per workgroup> out=<bf16|f32|f32acc|f32det> ksplit=<K shares> kper=<K tiles per share>"

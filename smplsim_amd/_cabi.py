@@ -144,7 +144,16 @@ FIELDS = {"qpos": 0, "qvel": 1, "xpos": 2, "xmat": 3, "body_vel": 4, "touch": 5,
 ACTIVATIONS = {"none": 0, "silu": 1, "tanh": 2, "relu": 3}
 MLP_EXPORTS = ["ss_linear_bf16", "ss_linear_bf16_train", "ss_linear_bf16_dx", "ss_wgrad_bf16", "ss_obs_to_bf16", "ss_gaussian_sample",
                "ss_debug_last_gemm", "ss_linear_bf16_dx_det", "ss_linear_bf16_dx_det_workspace", "ss_wgrad_bf16_det", "ss_wgrad_bf16_det_workspace",
-               "ss_ppo_policy_head", "ss_ppo_policy_head_workspace", "ss_value_head", "ss_value_head_workspace"]            # include/smplsim_mlp.h (product library only: the matrix-core kernels)
+               "ss_ppo_policy_head", "ss_ppo_policy_head_workspace", "ss_value_head", "ss_value_head_workspace", "ss_adam_step", "ss_adam_step_workspace"]            # include/smplsim_mlp.h (product library only: the matrix-core kernels)
+
+
+class AdamTensor(C.Structure):
+    """ss_adam_tensor of include/smplsim_mlp.h: one tensor of an ss_adam_step call."""
+    _fields_ = [("p", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("g", C.c_void_p), ("w_bf16", C.c_void_p), ("wt_bf16", C.c_void_p),
+                ("rows", C.c_int32), ("cols", C.c_int32), ("ldg", C.c_int32), ("ld_w", C.c_int32), ("ld_wt", C.c_int32)]
+
+
+ADAM_MAX_TENSORS = 32            # tensors of one ss_adam_step call (the table travels in the kernel arguments)
 
 
 def bind_mlp(lib):
@@ -166,6 +175,9 @@ def bind_mlp(lib):
     # (pred, target, M, dpred, ldd, dpred_is_bf16, loss, workspace, bytes, stream)
     lib.ss_value_head.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, C.c_int64, vp]
     lib.ss_value_head_workspace.argtypes = [C.c_int32]; lib.ss_value_head_workspace.restype = C.c_int64
+    # (tensors, count, step, lr, beta1, beta2, eps, weight_decay, max_grad_norm, grad_norm, workspace, bytes, stream)
+    lib.ss_adam_step.argtypes = [C.POINTER(AdamTensor), C.c_int32, C.c_int32] + [C.c_double] * 6 + [vp, vp, C.c_int64, vp]
+    lib.ss_adam_step_workspace.argtypes = [C.POINTER(AdamTensor), C.c_int32]; lib.ss_adam_step_workspace.restype = C.c_int64
     return lib
 
 

@@ -49,6 +49,7 @@ class PPOConfig:
     mfma_update: bool = False      # update: the networks' forward AND backward passes on the library's own GEMM (learning/fused_train.py), bf16 operands
     deterministic_update: bool = False   # with mfma_update: the update's reductions in a fixed order (same seed, same bits; DESIGN.md "deterministic update")
     fused_loss: bool = False       # update: surrogate, value loss and their gradients by the library's loss heads (learning/fused_loss.py), whichever path ran the networks
+    fused_optimizer: bool = False  # update: gradient clipping and Adam by the library's optimiser step (learning/fused_optim.py); with mfma_update it also keeps the bf16 weight images current
     extra: dict = field(default_factory=dict)
 
 
@@ -61,6 +62,8 @@ class AgentPPO:
             raise ValueError("deterministic_update applies to the mfma_update path only (the torch update paths are reproducible as they are)")
         if c.fused_loss and self.device.type != "cuda":
             raise RuntimeError("fused_loss needs the env on a GPU (the loss heads have no CPU path)")
+        if c.fused_optimizer and self.device.type != "cuda":
+            raise RuntimeError("fused_optimizer needs the env on a GPU (the optimiser step has no CPU path)")
         torch.manual_seed(seed)
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed)
@@ -69,8 +72,14 @@ class AgentPPO:
         self.value_net = Value(MLP(self.state_dim, c.hidden, c.activation)).to(self.device)
         # (with mfma_update: torch's single-kernel Adam — the same update rule; the default multi-tensor form is 8 launches per step, 3 ms of an 80 ms update)
         fused = dict(fused=True) if c.mfma_update and self.device.type == "cuda" else {}
-        self.optimizer_policy = torch.optim.Adam(self.policy_net.parameters(), lr=c.policy_lr, eps=1e-8, weight_decay=c.policy_weightdecay, **fused)
-        self.optimizer_value = torch.optim.Adam(self.value_net.parameters(), lr=c.value_lr, eps=1e-8, weight_decay=c.value_weightdecay, **fused)
+        if c.fused_optimizer:
+            # the library's step: the policy's gradient clipping happens inside it (update_params skips clip_grad_norm_); checkpoints are plain Adam's
+            from ..learning.fused_optim import LibAdam
+            self.optimizer_policy = LibAdam(self.policy_net.parameters(), lr=c.policy_lr, eps=1e-8, weight_decay=c.policy_weightdecay, max_grad_norm=c.policy_grad_clip)
+            self.optimizer_value = LibAdam(self.value_net.parameters(), lr=c.value_lr, eps=1e-8, weight_decay=c.value_weightdecay)
+        else:
+            self.optimizer_policy = torch.optim.Adam(self.policy_net.parameters(), lr=c.policy_lr, eps=1e-8, weight_decay=c.policy_weightdecay, **fused)
+            self.optimizer_value = torch.optim.Adam(self.value_net.parameters(), lr=c.value_lr, eps=1e-8, weight_decay=c.value_weightdecay, **fused)
         self.epoch, self.num_steps = 0, 0
         self.horizon = max(1, -(-c.min_batch_size // env.num_envs))
         self._obs = None
@@ -81,8 +90,13 @@ class AgentPPO:
         self.fused_policy = self.fused_value = None
         if c.mfma_update:
             from ..learning.fused_train import FusedMLPTrain
-            self.fused_policy = FusedMLPTrain(self.policy_net.net.affine_layers, self.policy_net.action_mean, c.activation, deterministic=c.deterministic_update)
-            self.fused_value = FusedMLPTrain(self.value_net.net.affine_layers, self.value_net.value_head, c.activation, deterministic=c.deterministic_update)
+            images = dict(weight_images=True) if c.fused_optimizer else {}      # the optimiser step writes the bf16 weight images the passes read
+            self.fused_policy = FusedMLPTrain(self.policy_net.net.affine_layers, self.policy_net.action_mean, c.activation, deterministic=c.deterministic_update, **images)
+            self.fused_value = FusedMLPTrain(self.value_net.net.affine_layers, self.value_net.value_head, c.activation, deterministic=c.deterministic_update, **images)
+            if c.fused_optimizer:
+                for opt, net in ((self.optimizer_policy, self.fused_policy), (self.optimizer_value, self.fused_value)):
+                    for w, wb, wt in net.images():
+                        opt.attach_images(w, w_bf16=wb, wt_bf16=wt)
         self.surrogate = self.value_mse = None
         if c.fused_loss:
             from ..learning.fused_loss import PPOSurrogate, ValueMSE
@@ -284,13 +298,15 @@ class AgentPPO:
             loss = self.ppo_loss(s_i, a_i, adv_i, flp_i)
             self.optimizer_policy.zero_grad(set_to_none=True)
             loss.backward()
-            if c.policy_grad_clip is not None:
+            if c.policy_grad_clip is not None and not c.fused_optimizer:      # (fused_optimizer: inside the step)
                 torch.nn.utils.clip_grad_norm_(self.policy_net.parameters(), c.policy_grad_clip)
             self.optimizer_policy.step()
             info["surr_loss"] = loss.detach()
         stats = getattr(getattr(self, "surrogate", None), "last_stats", None)
         if stats is not None:
             info["clip_frac"], info["approx_kl"] = stats[1], stats[2]   # of the last iteration, from the head's launch
+        if c.fused_optimizer:
+            info["grad_norm"] = self.optimizer_policy.last_grad_norm   # the policy's gradient norm before clipping, of the last iteration
         if self.fast_policy is not None:
             self.fast_policy.refresh()                          # bf16 snapshots of the updated weights for the sampler
         self.epoch += 1

@@ -27,6 +27,7 @@
 #include "ss_api.h"
 #include "ss_gemm256.h"
 #include "ss_ppo_head.h"
+#include "ss_optim.h"
 
 namespace {
 
@@ -1266,6 +1267,57 @@ int ss_value_head(const float *pred, const float *target, int32_t M, void *dpred
   if (dpred_is_bf16) hipLaunchKernelGGL(ppo_head::ss_value_head_kernel<true>, dim3((unsigned)P), dim3(256), 0, st, pred, target, M, dpred, ldd, part, 1.0 / M);
   else hipLaunchKernelGGL(ppo_head::ss_value_head_kernel<false>, dim3((unsigned)P), dim3(256), 0, st, pred, target, M, dpred, ldd, part, 1.0 / M);
   hipLaunchKernelGGL(ppo_head::ss_head_reduce_kernel, dim3(1), dim3(64), 0, st, part, P, 1, loss, 1, static_cast<float *>(nullptr), (double)M, 1.0);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
+}
+
+// ---- the optimiser step (ss_optim.h): three launches on `stream`, the descriptor table by value in the kernel arguments
+// Checks the descriptors and fills the kernels' table; returns the number of tiles, or -1 (ss_last_error set).
+static int64_t adam_table(const ss_adam_tensor *tensors, int32_t count, optim::Table &tb) {
+  if (!tensors) return fail(SS_ERR_INVALID, "null argument");
+  if (count < 1 || count > optim::MAX_TENSORS) return fail(SS_ERR_INVALID, "ss_adam_step: 1 <= count <= 32 tensors in one call");
+  int64_t tiles = 0;
+  for (int i = 0; i < count; i++) {
+    const ss_adam_tensor &d = tensors[i];
+    if (!d.p || !d.m || !d.v || !d.g) return fail(SS_ERR_INVALID, "null argument");
+    if (d.rows < 1 || d.cols < 1) return fail(SS_ERR_INVALID, "ss_adam_step: rows >= 1, cols >= 1");
+    if (d.ldg < d.cols || (d.w_bf16 && d.ld_w < d.cols) || (d.wt_bf16 && d.ld_wt < d.rows))
+      return fail(SS_ERR_INVALID, "ss_adam_step: row strides must be >= the row's width (ldg, ld_w >= cols; ld_wt >= rows)");
+    if ((d.w_bf16 && bad_bf16_grad(d.w_bf16, d.ld_w)) || (d.wt_bf16 && bad_bf16_grad(d.wt_bf16, d.ld_wt)))
+      return fail(SS_ERR_INVALID, "ss_adam_step: a bf16 image needs its row stride a multiple of 8 and a 16-byte aligned base");
+    tb.t[i] = optim::Tensor{d.p, d.m, d.v, d.g, static_cast<unsigned short *>(d.w_bf16), static_cast<unsigned short *>(d.wt_bf16), d.rows, d.cols, d.ldg,
+                            d.w_bf16 ? d.ld_w : 0, d.wt_bf16 ? d.ld_wt : 0, (int)tiles};
+    tiles += row_groups(d.rows, optim::TILE) * row_groups(d.cols, optim::TILE);
+    if (tiles > (1ll << 30)) return fail(SS_ERR_INVALID, "ss_adam_step: more than 2^30 tiles in one call");
+  }
+  tb.count = count;
+  return tiles;
+}
+
+int64_t ss_adam_step_workspace(const ss_adam_tensor *tensors, int32_t count) {
+  optim::Table tb{};
+  const int64_t tiles = adam_table(tensors, count, tb);
+  return tiles < 0 ? -1 : (tiles + 1) * 8;
+}
+
+int ss_adam_step(const ss_adam_tensor *tensors, int32_t count, int32_t step, double lr, double beta1, double beta2, double eps, double weight_decay,
+                 double max_grad_norm, float *grad_norm, void *workspace, int64_t workspace_bytes, void *stream) {
+  optim::Table tb{};
+  const int64_t tiles = adam_table(tensors, count, tb);
+  if (tiles < 0) return SS_ERR_INVALID;
+  if (step < 1) return fail(SS_ERR_INVALID, "ss_adam_step: step >= 1");
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(SS_ERR_INVALID, "ss_adam_step: the betas must lie in [0, 1)");
+  if (!(eps >= 0.0)) return fail(SS_ERR_INVALID, "ss_adam_step: eps >= 0");
+  if (lr != lr || weight_decay != weight_decay || max_grad_norm != max_grad_norm) return fail(SS_ERR_INVALID, "ss_adam_step: lr, weight_decay and max_grad_norm must not be NaN");
+  if (check_workspace(workspace, workspace_bytes, (tiles + 1) * 8) != SS_OK) return SS_ERR_INVALID;
+  const bool clip = max_grad_norm > 0.0 && max_grad_norm < HUGE_VAL;
+  const optim::Hyper h{clip ? max_grad_norm : 0.0, weight_decay, beta1, beta2, lr / (1.0 - pow(beta1, (double)step)), sqrt(1.0 - pow(beta2, (double)step)), eps};
+  double *part = static_cast<double *>(workspace);
+  hipStream_t st = (hipStream_t)stream;
+  const int T = (int)tiles;
+  hipLaunchKernelGGL(optim::ss_adam_sumsq_kernel, dim3((unsigned)T), dim3(256), 0, st, tb, part);
+  hipLaunchKernelGGL(optim::ss_adam_reduce_kernel, dim3(1), dim3(64), 0, st, part, T, grad_norm);
+  hipLaunchKernelGGL(optim::ss_adam_step_kernel, dim3((unsigned)T), dim3(256), 0, st, tb, static_cast<const double *>(part), T, h);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
 }

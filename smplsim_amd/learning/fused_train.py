@@ -2,7 +2,8 @@
 
 What it replaces: autograd over torch.nn.Linear + activation under bf16 autocast (hipBLASLt GEMMs plus separate bias, activation,
 cast and transpose launches) in the reference's update_policy / update_value (agents/agent_ppo.py:20-83).  The loss, the optimiser,
-the gradient clipping and the RunningNorm stay torch code and untouched; only `y = head(MLP(x))` and its backward are here:
+the gradient clipping and the RunningNorm are not here (learning/fused_loss.py and learning/fused_optim.py have the first three); only `y = head(MLP(x))` and its
+backward are:
 
   forward, per hidden layer   h = act(z), g = act'(z)   with z = h_below W^T + b     ONE launch: the result and the activation's derivative from one tile
   head                        y = h W^T + b in fp32 (the inference kernel: the action mean must not be rounded to bf16)
@@ -64,7 +65,7 @@ class _FusedMLP(torch.autograd.Function):
     """y = Linear_{L+1}(act(Linear_L(... act(Linear_1(x))))) with x [M, D] fp32; params = W_1, b_1, ..., W_{L+1}, b_{L+1} (fp32, torch.nn.Linear layout)."""
 
     @staticmethod
-    def forward(ctx, x, act, bufs, track, det, *params):
+    def forward(ctx, x, act, bufs, track, det, images, *params):
         dev, st = x.device, _launch_stream(x.device)
         ws, bs = params[0::2], params[1::2]
         nl = len(ws)
@@ -82,8 +83,12 @@ class _FusedMLP(torch.autograd.Function):
         h[:M, :D] = x
         hs, gs, wbs = [h], [], []
         # the layers' weights in bf16, all by one multi-tensor copy (they change with every optimiser step; 7 launches a pass otherwise)
-        wb_all = [bufs.get(("w", i), (ws[i].shape[0], kpad[i]), bf, dev, fresh) for i in range(nl)]
-        torch._foreach_copy_([wb_all[i][:, :ws[i].shape[1]] for i in range(nl)], [w_.detach() for w_ in ws])
+        # (weight_images: the owner's persistent images, kept current by the optimiser step: no copy here)
+        if images is not None:
+            wb_all = images.w
+        else:
+            wb_all = [bufs.get(("w", i), (ws[i].shape[0], kpad[i]), bf, dev, fresh) for i in range(nl)]
+            torch._foreach_copy_([wb_all[i][:, :ws[i].shape[1]] for i in range(nl)], [w_.detach() for w_ in ws])
         for i in range(nl - 1):
             w = ws[i]
             N = w.shape[0]
@@ -102,6 +107,7 @@ class _FusedMLP(torch.autograd.Function):
                                     _cabi.ACTIVATIONS["none"], 1, st))
         ctx.act, ctx.M, ctx.Mp, ctx.kpad, ctx.dims = act, M, Mp, kpad, [(w_.shape[0], w_.shape[1]) for w_ in ws]
         ctx.det = det
+        ctx.wts = images.wt if images is not None else None
         ctx.hs, ctx.gs, ctx.wbs = hs, gs, wbs
         return out[:M]
 
@@ -147,8 +153,10 @@ class _FusedMLP(torch.autograd.Function):
             offs.append(offs[-1] + _pad(z, 64))
         flat = torch.zeros(offs[-1], dtype=torch.float32, device=dev)
         # W^T of every layer but the first (the "W" operand of the dX products), all by one multi-tensor copy
-        wts = {i: bufs.get(("wt", i), (kpad[i], nhp if i == nl - 1 else dims[i][0]), bf, dev, fresh) for i in range(1, nl)}
-        torch._foreach_copy_([wts[i][:, :dims[i][0]] for i in range(1, nl)], [ctx.wbs[i].t() for i in range(1, nl)])
+        wts = ctx.wts
+        if wts is None:
+            wts = {i: bufs.get(("wt", i), (kpad[i], nhp if i == nl - 1 else dims[i][0]), bf, dev, fresh) for i in range(1, nl)}
+            torch._foreach_copy_([wts[i][:, :dims[i][0]] for i in range(1, nl)], [ctx.wbs[i].t() for i in range(1, nl)])
         for i in range(nl - 1, -1, -1):
             n_out, n_in = dims[i]
             n_outp = dz.shape[1]
@@ -171,17 +179,52 @@ class _FusedMLP(torch.autograd.Function):
                     db = None
                     _linear_train(dz, wt, None, ctx.gs[i - 1], dzb, None, None, Mp, nb, n_outp, nb, 0, none, False, st)
                 dz = dzb
-        ctx.hs = ctx.gs = ctx.wbs = None
+        ctx.hs = ctx.gs = ctx.wbs = ctx.wts = None
         if ctx.bufs is not None:
             ctx.bufs.busy = False
-        return (None, None, None, None, None, *grads)
+        return (None, None, None, None, None, None, *grads)
+
+
+class _WeightImages:
+    """Persistent bf16 images of a FusedMLPTrain's weights, in the layouts the passes read: w[i] = W_i [n_out, kpad_i] for the forward products, wt[i] = W_i^T
+    [kpad_i, n_out (the head's padded to 128)] for the dX products of every layer but the first.  The pads are zeroed once, here, and never written again.  Not
+    part of _Buffers' fresh / busy logic: a graph whose backward runs after a later optimiser step sees that step's W^T."""
+
+    def __init__(self, layers):
+        nl = len(layers)
+        dev, bf = layers[0].weight.device, torch.bfloat16
+        dims = [tuple(l.weight.shape) for l in layers]
+        kpad = [_pad(d[1], 128) if i == 0 else _pad(d[1], 64) for i, d in enumerate(dims)]
+        self.layers = layers
+        self.w = [torch.zeros(dims[i][0], kpad[i], dtype=bf, device=dev) for i in range(nl)]
+        self.wt = {i: torch.zeros(kpad[i], _pad(dims[i][0], 128) if i == nl - 1 else dims[i][0], dtype=bf, device=dev) for i in range(1, nl)}
+        self.versions = [None] * nl                                # each weight's torch version when its images were last known current
+
+    def refresh_moved(self):
+        """Re-cast the images of every weight that torch has written in place since they were last current (load_state_dict, a torch optimiser): the copies the
+        passes made before.  The library's optimiser step writes weight and images together through raw pointers and leaves the version alone, so the usual
+        call costs one integer compare per layer and no launch."""
+        moved = [i for i, l in enumerate(self.layers) if l.weight._version != self.versions[i]]
+        if not moved:
+            return
+        ws = [self.layers[i].weight.detach() for i in moved]
+        torch._foreach_copy_([self.w[i][:, :w.shape[1]] for i, w in zip(moved, ws)], ws)
+        tr = [i for i in moved if i > 0]
+        if tr:
+            torch._foreach_copy_([self.wt[i][:self.layers[i].weight.shape[1], :self.layers[i].weight.shape[0]] for i in tr], [self.w[i][:, :self.layers[i].weight.shape[1]].t() for i in tr])
+        for i in moved:
+            self.versions[i] = self.layers[i].weight._version
 
 
 class FusedMLPTrain:
     """Callable over an existing stack of torch.nn.Linear layers (the hidden ones followed by `act`, then the head): differentiable with
-    respect to the layers' parameters, not to the input (the update's inputs are rollout states)."""
+    respect to the layers' parameters, not to the input (the update's inputs are rollout states).
 
-    def __init__(self, hidden_layers, head, activation_name, deterministic=False):
+    weight_images=True: the bf16 images of the weights (W and W^T, which every pass otherwise re-casts from the fp32 weights) are persistent and expected to be
+    kept current by the optimiser: `images()` lists them for LibAdam.attach_images (learning/fused_optim.py), whose step writes them next to the fp32 weight.
+    A weight that torch itself writes in place is noticed by its version counter and its images are re-cast before the next pass."""
+
+    def __init__(self, hidden_layers, head, activation_name, deterministic=False, weight_images=False):
         if activation_name not in _cabi.ACTIVATIONS or activation_name == "none":
             raise ValueError(f"activation {activation_name!r} has no fused epilogue (silu, tanh, relu)")
         self.layers = list(hidden_layers) + [head]
@@ -191,10 +234,19 @@ class FusedMLPTrain:
             raise RuntimeError("FusedMLPTrain needs the networks on a GPU (there is no CPU path)")
         self.deterministic = bool(deterministic)                  # the backward pass's reductions in a fixed order (module docstring)
         self.bufs, self.bufs_nograd = _Buffers(), _Buffers()
+        self.weight_images = _WeightImages(self.layers) if weight_images else None
+
+    def images(self):
+        """[(weight, w_bf16, wt_bf16 or None)] per layer: the arguments of LibAdam.attach_images."""
+        if self.weight_images is None:
+            raise RuntimeError("FusedMLPTrain was built without weight_images")
+        return [(l.weight, self.weight_images.w[i], self.weight_images.wt.get(i)) for i, l in enumerate(self.layers)]
 
     def __call__(self, x):
+        if self.weight_images is not None:
+            self.weight_images.refresh_moved()
         params = []
         for l in self.layers:
             params += [l.weight, l.bias]
         track = torch.is_grad_enabled()                           # (inside Function.forward the grad mode is always off)
-        return _FusedMLP.apply(x.detach().float(), self.act, self.bufs if track else self.bufs_nograd, track, self.deterministic, *params)
+        return _FusedMLP.apply(x.detach().float(), self.act, self.bufs if track else self.bufs_nograd, track, self.deterministic, self.weight_images, *params)
