@@ -6,7 +6,7 @@
  * GEMM-shaped (4096 x 289 -> 2048 -> 1536 -> 1024 -> 1024 -> 512 -> 512 -> 69: 59 GFLOP per env step) and sits in the
  * sampling loop next to ss_step, so it runs on the matrix cores: bf16 operands, fp32 accumulation
  * (v_mfma_f32_32x32x16_bf16), bias + activation fused into the GEMM's epilogue, activations kept in bf16 between layers.
- * The PPO update's products, loss heads and optimiser step (ss_adam_step) follow below; the chain rule between them stays with the caller.
+ * The PPO update's products, loss heads, optimiser step (ss_adam_step) and RunningNorm update follow below; the chain rule between them stays with the caller.
  *
  * Conventions as in smplsim_hip.h: device pointers, int status + ss_last_error(), work enqueued on the caller's stream.
  */
@@ -181,6 +181,34 @@ typedef struct ss_adam_tensor {
 int ss_adam_step(const ss_adam_tensor *tensors, int32_t count, int32_t step, double lr, double beta1, double beta2, double eps, double weight_decay,
                  double max_grad_norm, float *grad_norm, void *workspace, int64_t workspace_bytes, void *stream);
 int64_t ss_adam_step_workspace(const ss_adam_tensor *tensors, int32_t count);
+
+/* ss_running_norm_update: RunningNorm.update of the policy's observation normalisation on the device (learning/networks.py; the reference's running_norm.py:22-29,
+ * which the update runs in train mode once per optimisation iteration): the biased column statistics bm, bv of x [M, dim] (fp32, row stride ldx >= dim, any
+ * 4-byte-aligned base) merged into the running statistics, in place:
+ *   w = n / (n + M);   var' = w var + (1 - w) bv + w (1 - w) (bm - mean)^2;   mean' = w mean + (1 - w) bm;   std' = sqrt(var');   n' = n + M
+ * mean, var, std [dim] f32 and n [1] int64, all on the device.  The normalised bf16 operand of the network is ss_obs_to_bf16 called after this with the same pointers.
+ * Reproducible like the loss heads and ss_adam_step: no atomics, every output a function of the arguments and the input bytes alone — not of the order in which
+ * workgroups run, nor of what the workspace held before.  Every value is formed in fp64 from the fp32 inputs and rounded to fp32 once, when it is stored; std' is the
+ * fp32 rounding of the fp64 square root of the STORED fp32 var' (so a checkpoint's std stays var.sqrt() to 1 ulp).  Two launches on `stream` (partials, merge), no
+ * host synchronisation, nothing read back; the workspace is caller-owned, 16-byte aligned, and may be reused by the next call on the same stream.
+ * A NaN in column c makes mean'[c], var'[c] and std'[c] NaN and changes no other column; var' is never negative; a constant column gives bv = 0 and bm = the constant
+ * exactly (from n = 0: var' = 0, mean' = the constant).
+ *   workspace  at least ss_running_norm_workspace(M, dim) = ceil(M / SS_NORM_BLOCK_ROWS) * dim * 16 bytes.  After the call it holds, for row block b and column c, two
+ *              doubles at workspace[(b * dim + c) * 2]: the mean of column c over the rows [256 b, min(256 b + 256, M)) and the sum of the squared deviations from that
+ *              mean (M2), never negative.
+ *   order      a block: workgroup (b, g) owns the columns 64 g .. 64 g + 63, one per lane; lane l of wavefront w adds d = x - K and d * d over the rows
+ *              256 b + 64 w .. 256 b + 64 w + 63 (those below M) of column 64 g + l in ascending order, K being the block's first row in that column; the four
+ *              wavefronts meet as ((w_0 + w_1) + w_2) + w_3 = S1, S2; mean = K + S1 / rows, M2 = S2 - S1 * S1 / rows (a negative result stored as 0).
+ *              the merge: one workgroup, thread t owns the columns t, t + 256, ...; the blocks are folded ascending from block 0 by the pairwise formula, with
+ *              n_a the rows folded so far and n_b those of the next block: f = n_b / (n_a + n_b); delta = mean_b - mean_a; mean_a += delta * f;
+ *              M2_a += M2_b + delta * delta * (n_a * f).  Then bm = mean_a, bv = M2_a / M and the formulas above with w = (double)n / (double)(n + M) and 1 - w
+ *              formed from that w.  Every thread reads n before a barrier; thread 0 stores n' after it.
+ * SS_ERR_INVALID, nothing launched: a null required pointer, M < 1 or dim < 1, ldx < dim, a null, misaligned or too-small workspace, more than 2^24 workgroups
+ * (ceil(M / 256) * ceil(dim / 64): beyond any device's memory).  The query returns a negative value (and sets ss_last_error) for M < 1 or dim < 1. */
+#define SS_NORM_BLOCK_ROWS 256
+int64_t ss_running_norm_workspace(int32_t M, int32_t dim);
+int ss_running_norm_update(const float *x, int32_t M, int32_t dim, int32_t ldx, float *mean, float *var, float *std, int64_t *n, void *workspace,
+                           int64_t workspace_bytes, void *stream);
 
 /* Test hook: the GEMM instantiation launched last by an ss_linear_* / ss_wgrad_bf16* call on the calling host thread, as
  * "<family> mode=<G256 mode or -> bn=<BN> bk=<BK> waves=<waves per workgroup> out=<bf16|f32|f32acc|f32det> ksplit=<K shares> kper=<K tiles per share>"

@@ -144,7 +144,8 @@ FIELDS = {"qpos": 0, "qvel": 1, "xpos": 2, "xmat": 3, "body_vel": 4, "touch": 5,
 ACTIVATIONS = {"none": 0, "silu": 1, "tanh": 2, "relu": 3}
 MLP_EXPORTS = ["ss_linear_bf16", "ss_linear_bf16_train", "ss_linear_bf16_dx", "ss_wgrad_bf16", "ss_obs_to_bf16", "ss_gaussian_sample",
                "ss_debug_last_gemm", "ss_linear_bf16_dx_det", "ss_linear_bf16_dx_det_workspace", "ss_wgrad_bf16_det", "ss_wgrad_bf16_det_workspace",
-               "ss_ppo_policy_head", "ss_ppo_policy_head_workspace", "ss_value_head", "ss_value_head_workspace", "ss_adam_step", "ss_adam_step_workspace"]            # include/smplsim_mlp.h (product library only: the matrix-core kernels)
+               "ss_ppo_policy_head", "ss_ppo_policy_head_workspace", "ss_value_head", "ss_value_head_workspace", "ss_adam_step", "ss_adam_step_workspace",
+               "ss_running_norm_update", "ss_running_norm_workspace"]            # include/smplsim_mlp.h (product library only: the matrix-core kernels)
 
 
 class AdamTensor(C.Structure):
@@ -154,6 +155,7 @@ class AdamTensor(C.Structure):
 
 
 ADAM_MAX_TENSORS = 32            # tensors of one ss_adam_step call (the table travels in the kernel arguments)
+NORM_BLOCK_ROWS = 256            # SS_NORM_BLOCK_ROWS: rows per (mean, M2) pair in the workspace of ss_running_norm_update
 
 
 def bind_mlp(lib):
@@ -178,6 +180,9 @@ def bind_mlp(lib):
     # (tensors, count, step, lr, beta1, beta2, eps, weight_decay, max_grad_norm, grad_norm, workspace, bytes, stream)
     lib.ss_adam_step.argtypes = [C.POINTER(AdamTensor), C.c_int32, C.c_int32] + [C.c_double] * 6 + [vp, vp, C.c_int64, vp]
     lib.ss_adam_step_workspace.argtypes = [C.POINTER(AdamTensor), C.c_int32]; lib.ss_adam_step_workspace.restype = C.c_int64
+    # (x, M, dim, ldx, mean, var, std, n, workspace, bytes, stream)
+    lib.ss_running_norm_update.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int64, vp]
+    lib.ss_running_norm_workspace.argtypes = [C.c_int32, C.c_int32]; lib.ss_running_norm_workspace.restype = C.c_int64
     return lib
 
 

@@ -50,6 +50,7 @@ class PPOConfig:
     deterministic_update: bool = False   # with mfma_update: the update's reductions in a fixed order (same seed, same bits; DESIGN.md "deterministic update")
     fused_loss: bool = False       # update: surrogate, value loss and their gradients by the library's loss heads (learning/fused_loss.py), whichever path ran the networks
     fused_optimizer: bool = False  # update: gradient clipping and Adam by the library's optimiser step (learning/fused_optim.py); with mfma_update it also keeps the bf16 weight images current
+    fused_norm: bool = False       # with mfma_update: the policy's train-mode RunningNorm by the library's kernels (learning/fused_norm.py) and the networks' bf16 inputs made once, not once per pass
     extra: dict = field(default_factory=dict)
 
 
@@ -64,6 +65,10 @@ class AgentPPO:
             raise RuntimeError("fused_loss needs the env on a GPU (the loss heads have no CPU path)")
         if c.fused_optimizer and self.device.type != "cuda":
             raise RuntimeError("fused_optimizer needs the env on a GPU (the optimiser step has no CPU path)")
+        if c.fused_norm and not c.mfma_update:
+            raise ValueError("fused_norm applies to the mfma_update path only (it hands the networks' passes their bf16 operands)")
+        if c.fused_norm and self.device.type != "cuda":
+            raise RuntimeError("fused_norm needs the env on a GPU (the RunningNorm kernels have no CPU path)")
         torch.manual_seed(seed)
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed)
@@ -97,6 +102,10 @@ class AgentPPO:
                 for opt, net in ((self.optimizer_policy, self.fused_policy), (self.optimizer_value, self.fused_value)):
                     for w, wb, wt in net.images():
                         opt.attach_images(w, w_bf16=wb, wt_bf16=wt)
+        self.lib_norm = None
+        if c.fused_norm:
+            from ..learning.fused_norm import LibRunningNorm
+            self.lib_norm = LibRunningNorm(self.policy_net.norm)
         self.surrogate = self.value_mse = None
         if c.fused_loss:
             from ..learning.fused_loss import PPOSurrogate, ValueMSE
@@ -226,11 +235,17 @@ class AgentPPO:
     def _f32(self, x):
         return x.float() if x.dtype == torch.bfloat16 else x
 
+    def _policy_input(self, states):
+        """What the policy's pass on the library's GEMM reads: RunningNorm(states) (train mode: its statistics follow the passes as in the torch path) — by torch as
+        an fp32 tensor, or with fused_norm by the library's kernels as the pass's bf16 operand."""
+        lib_norm = getattr(self, "lib_norm", None)
+        return lib_norm(states) if lib_norm is not None else self.policy_net.norm(states)
+
     def _policy_log_prob(self, states, actions):
-        """PolicyGaussian.get_log_prob with the network passes on the library's GEMM (mfma_update): RunningNorm (train mode: its statistics
-        follow the passes as in the torch path), mean = head(MLP(.)), the log-density in fp32 torch."""
+        """PolicyGaussian.get_log_prob with the network passes on the library's GEMM (mfma_update): RunningNorm (_policy_input), mean = head(MLP(.)), the
+        log-density in fp32 torch."""
         p = self.policy_net
-        mean = self.fused_policy(p.norm(states))
+        mean = self.fused_policy(self._policy_input(states))
         log_std = p.action_log_std.expand_as(mean)
         z = (actions - mean) * torch.exp(-log_std)
         terms = -0.5 * z * z - log_std - 0.5 * math.log(2.0 * math.pi)
@@ -242,7 +257,7 @@ class AgentPPO:
             # fused_loss: the head's fp32 mean from whichever path runs the network; log-density, surrogate and both gradients in ss_ppo_policy_head
             p = self.policy_net
             if self.fused_policy is not None:
-                mean = self.fused_policy(p.norm(states))
+                mean = self.fused_policy(self._policy_input(states))
             else:
                 with self._autocast():
                     mean = self._f32(p.mean_and_log_std(states)[0])
@@ -257,6 +272,7 @@ class AgentPPO:
         return -torch.minimum(ratio * advantages, clipped * advantages).mean()
 
     def update_value(self, critic_states, returns):
+        """critic_states: the fp32 states, or (fused_norm) the critic's Bf16Operand of them."""
         for _ in range(self.cfg.value_opt_niter):
             if getattr(self, "fused_value", None) is not None:
                 pred = self.fused_value(critic_states)
@@ -278,7 +294,9 @@ class AgentPPO:
             # the critic's passes for GAE: on the library's GEMM with mfma_update, under the update's bf16 autocast with amp_bf16 (round 6: they ran
             # in fp32 whatever the update's precision was: 0.8 TFLOP at the fp32 rate, 8 ms of a 116 ms update), fp32 otherwise (the reference)
             vf = self.fused_value if getattr(self, "fused_value", None) is not None else self.value_net
-            values = self._f32(vf(states)).reshape(T, N)
+            # fused_norm: the critic's bf16 operand of the states, cast once here for GAE's pass and every critic pass of the update (they re-cast the same tensor otherwise)
+            critic_states = self.fused_value.operand(states) if c.fused_norm else states
+            values = self._f32(vf(critic_states)).reshape(T, N)
             boot = self._f32(vf(batch["last_state"])).reshape(N) if c.bootstrap else None
         adv, ret = estimate_advantages_columns(batch["rewards"], batch["not_done"], batch["not_dead"], values, c.gamma, c.tau, boot)
         adv = normalize_advantages(adv).reshape(T * N, 1)
@@ -294,7 +312,7 @@ class AgentPPO:
         s_i, a_i, adv_i, flp_i = states[ind], actions[ind], adv[ind], fixed_log_probs[ind]
         info = {}
         for _ in range(c.opt_num_epochs):
-            info["value_loss"] = self.update_value(states, ret)
+            info["value_loss"] = self.update_value(critic_states, ret)
             loss = self.ppo_loss(s_i, a_i, adv_i, flp_i)
             self.optimizer_policy.zero_grad(set_to_none=True)
             loss.backward()

@@ -28,6 +28,7 @@
 #include "ss_gemm256.h"
 #include "ss_ppo_head.h"
 #include "ss_optim.h"
+#include "ss_norm.h"
 
 namespace {
 
@@ -1318,6 +1319,34 @@ int ss_adam_step(const ss_adam_tensor *tensors, int32_t count, int32_t step, dou
   hipLaunchKernelGGL(optim::ss_adam_sumsq_kernel, dim3((unsigned)T), dim3(256), 0, st, tb, part);
   hipLaunchKernelGGL(optim::ss_adam_reduce_kernel, dim3(1), dim3(64), 0, st, part, T, grad_norm);
   hipLaunchKernelGGL(optim::ss_adam_step_kernel, dim3((unsigned)T), dim3(256), 0, st, tb, static_cast<const double *>(part), T, h);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
+}
+
+// ---- RunningNorm.update (ss_norm.h): two launches on `stream`, the blocks' (mean, M2) pairs into the caller's workspace, then the fixed-order fold and the running merge
+static int64_t running_norm_bytes(int32_t M, int32_t dim) { return row_groups(M, run_norm::BLOCK_ROWS) * dim * 16; }
+
+int64_t ss_running_norm_workspace(int32_t M, int32_t dim) {
+  if (M < 1 || dim < 1) {
+    fail(SS_ERR_INVALID, "ss_running_norm_workspace: M >= 1, dim >= 1");
+    return -1;
+  }
+  return running_norm_bytes(M, dim);
+}
+
+int ss_running_norm_update(const float *x, int32_t M, int32_t dim, int32_t ldx, float *mean, float *var, float *sd, int64_t *n, void *workspace,
+                           int64_t workspace_bytes, void *stream) {
+  if (!x || !mean || !var || !sd || !n) return fail(SS_ERR_INVALID, "null argument");
+  if (M < 1 || dim < 1) return fail(SS_ERR_INVALID, "ss_running_norm_update: M >= 1, dim >= 1");
+  if (ldx < dim) return fail(SS_ERR_INVALID, "ss_running_norm_update: row strides must be >= dim");
+  if (check_workspace(workspace, workspace_bytes, running_norm_bytes(M, dim)) != SS_OK) return SS_ERR_INVALID;
+  const int64_t P = row_groups(M, run_norm::BLOCK_ROWS), groups = row_groups(dim, run_norm::COLS);
+  if (P * groups >= (1ll << 24)) return fail(SS_ERR_INVALID, "ss_running_norm_update: more than 2^24 workgroups (M / 256 row blocks x dim / 64 column groups)");
+  double *part = static_cast<double *>(workspace);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(run_norm::ss_norm_partials_kernel, dim3((unsigned)(P * groups)), dim3(256), 0, st, x, M, dim, ldx, (int)groups, part);
+  hipLaunchKernelGGL(run_norm::ss_norm_merge_kernel, dim3(1), dim3(256), 0, st, static_cast<const double *>(part), (int)P, M, dim, mean, var, sd,
+                     reinterpret_cast<long long *>(n));
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
 }

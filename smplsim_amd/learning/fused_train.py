@@ -1,9 +1,9 @@
 """The PPO update's network passes on this library's own matrix-core GEMMs (include/smplsim_mlp.h: ss_linear_bf16_train, ss_wgrad_bf16).
 
 What it replaces: autograd over torch.nn.Linear + activation under bf16 autocast (hipBLASLt GEMMs plus separate bias, activation,
-cast and transpose launches) in the reference's update_policy / update_value (agents/agent_ppo.py:20-83).  The loss, the optimiser,
-the gradient clipping and the RunningNorm are not here (learning/fused_loss.py and learning/fused_optim.py have the first three); only `y = head(MLP(x))` and its
-backward are:
+cast and transpose launches) in the reference's update_policy / update_value (agents/agent_ppo.py:20-83).  The loss, the optimiser
+and the gradient clipping are not here (learning/fused_loss.py and learning/fused_optim.py have them; learning/fused_norm.py has the RunningNorm in front of the
+policy, which hands its result over as a Bf16Operand); only `y = head(MLP(x))` and its backward are:
 
   forward, per hidden layer   h = act(z), g = act'(z)   with z = h_below W^T + b     ONE launch: the result and the activation's derivative from one tile
   head                        y = h W^T + b in fp32 (the inference kernel: the action mean must not be rounded to bf16)
@@ -61,15 +61,27 @@ class _Buffers:
         return t
 
 
+class Bf16Operand:
+    """The first layer's operand of a FusedMLPTrain pass, made by the caller: t [pad(M, 128), pad(D, 128)] bf16, contiguous, rows >= M and columns >= D zero —
+    what the pass builds from an fp32 [M, D] input by `t[:M, :D] = x`.  The pass reads it in its forward AND in its backward (the first layer's weight gradient)
+    and never writes it: it must stay unchanged until that pass's backward has run (in stream order), or for good if no backward follows."""
+    __slots__ = ("t", "M", "D")
+
+    def __init__(self, t, M, D):
+        self.t, self.M, self.D = t, int(M), int(D)
+
+
 class _FusedMLP(torch.autograd.Function):
-    """y = Linear_{L+1}(act(Linear_L(... act(Linear_1(x))))) with x [M, D] fp32; params = W_1, b_1, ..., W_{L+1}, b_{L+1} (fp32, torch.nn.Linear layout)."""
+    """y = Linear_{L+1}(act(Linear_L(... act(Linear_1(x))))) with x [M, D] fp32 or a Bf16Operand; params = W_1, b_1, ..., W_{L+1}, b_{L+1} (fp32, torch.nn.Linear layout)."""
 
     @staticmethod
     def forward(ctx, x, act, bufs, track, det, images, *params):
-        dev, st = x.device, _launch_stream(x.device)
+        given = x if isinstance(x, Bf16Operand) else None          # (checked by FusedMLPTrain.__call__)
+        dev = given.t.device if given is not None else x.device
+        st = _launch_stream(dev)
         ws, bs = params[0::2], params[1::2]
         nl = len(ws)
-        M, D = x.shape
+        M, D = (given.M, given.D) if given is not None else x.shape
         Mp = _pad(M, 128)                                          # the batch is the K of the weight-gradient products; its pad rows are zero in every
                                                                    # dZ (zero rows of the head's gradient stay zero through (dZ W) * g), so what the
                                                                    # forward pass leaves in the pad rows of h (act(bias)) never reaches a gradient
@@ -79,8 +91,11 @@ class _FusedMLP(torch.autograd.Function):
             bufs.busy = True
         ctx.bufs = bufs if track and not fresh else None
         bf = torch.bfloat16
-        h = bufs.get("x", (Mp, kpad[0]), bf, dev, fresh)           # (pad rows and columns stay zero: only [:M, :D] is ever written)
-        h[:M, :D] = x
+        if given is not None:
+            h = given.t                                            # read here and by the backward pass's first weight gradient; never written
+        else:
+            h = bufs.get("x", (Mp, kpad[0]), bf, dev, fresh)       # (pad rows and columns stay zero: only [:M, :D] is ever written)
+            h[:M, :D] = x
         hs, gs, wbs = [h], [], []
         # the layers' weights in bf16, all by one multi-tensor copy (they change with every optimiser step; 7 launches a pass otherwise)
         # (weight_images: the owner's persistent images, kept current by the optimiser step: no copy here)
@@ -242,11 +257,38 @@ class FusedMLPTrain:
             raise RuntimeError("FusedMLPTrain was built without weight_images")
         return [(l.weight, self.weight_images.w[i], self.weight_images.wt.get(i)) for i, l in enumerate(self.layers)]
 
+    def operand(self, x):
+        """The pass's own first-layer operand of an fp32 [M, D] input, made once for several passes over the same input (the critic's states: every iteration of an
+        update reads them unchanged): a fresh zeroed [pad(M, 128), pad(D, 128)] bf16 tensor with the cast the pass does (`t[:M, :D] = x`).  `net(net.operand(x))` is
+        `net(x)` bit for bit.  The operand must stay unchanged until the backward of every pass that took it has run (Bf16Operand)."""
+        D = self.layers[0].weight.shape[1]
+        if x.dim() != 2 or x.shape[1] != D or x.shape[0] < 1:
+            raise ValueError(f"FusedMLPTrain.operand: an [M >= 1, {D}] input")
+        M = x.shape[0]
+        t = torch.zeros(_pad(M, 128), _pad(D, 128), dtype=torch.bfloat16, device=self.layers[0].weight.device)
+        t[:M, :D] = x.detach().float()
+        return Bf16Operand(t, M, D)
+
+    def _check_operand(self, op):
+        D, dev = self.layers[0].weight.shape[1], self.layers[0].weight.device
+        t = op.t
+        if not torch.is_tensor(t) or t.dtype != torch.bfloat16:
+            raise ValueError("Bf16Operand: the tensor must be bf16")
+        if t.device != dev:
+            raise ValueError(f"Bf16Operand: the tensor must be on the network's device ({dev})")
+        if op.D != D or op.M < 1 or tuple(t.shape) != (_pad(op.M, 128), _pad(D, 128)) or not t.is_contiguous():
+            raise ValueError(f"Bf16Operand: a contiguous [pad(M, 128), {_pad(D, 128)}] tensor with D = {D} (got {tuple(t.shape)}, M = {op.M}, D = {op.D})")
+
     def __call__(self, x):
+        """x: an fp32 [M, D] tensor, or a Bf16Operand (operand(); LibRunningNorm of learning/fused_norm.py) that the pass then uses as it is, without the cast."""
         if self.weight_images is not None:
             self.weight_images.refresh_moved()
         params = []
         for l in self.layers:
             params += [l.weight, l.bias]
         track = torch.is_grad_enabled()                           # (inside Function.forward the grad mode is always off)
-        return _FusedMLP.apply(x.detach().float(), self.act, self.bufs if track else self.bufs_nograd, track, self.deterministic, self.weight_images, *params)
+        if isinstance(x, Bf16Operand):
+            self._check_operand(x)
+        else:
+            x = x.detach().float()
+        return _FusedMLP.apply(x, self.act, self.bufs if track else self.bufs_nograd, track, self.deterministic, self.weight_images, *params)

@@ -33,6 +33,7 @@ def main():
     ap.add_argument("--deterministic-update", action="store_true", help="with --mfma-update: the update's reductions in a fixed order (same seed, same parameters)")
     ap.add_argument("--fused-loss", action="store_true", help="update: surrogate, value loss and their gradients by the library's loss heads (adds clip_frac and approx_kl to the log line)")
     ap.add_argument("--fused-optimizer", action="store_true", help="update: gradient clipping and Adam by the library's optimiser step (learning/fused_optim.py; adds grad_norm to the log line)")
+    ap.add_argument("--fused-norm", action="store_true", help="with --mfma-update: the policy's train-mode RunningNorm by the library's kernels and the networks' bf16 inputs made once (learning/fused_norm.py)")
     ap.add_argument("--save", default="")
     ap.add_argument("--log-every", type=int, default=1)
     ap.add_argument("--motion-file", default="", help="HumanoidIm: AMASS-style pickle ({key: {pose_aa, trans, fps}}); default = synthetic clips")
@@ -54,7 +55,7 @@ def main():
     else:
         env = SMPLSimVecEnv(args.envs, task=args.task, autoreset=True, seed=0)
     cfg = PPOConfig(hidden=tuple(int(x) for x in args.hidden.split(",")), min_batch_size=args.min_batch_size, opt_num_epochs=args.opt_epochs, amp_bf16=args.amp_bf16, mfma_inference=args.mfma_inference, mfma_update=args.mfma_update,
-                    deterministic_update=args.deterministic_update, fused_loss=args.fused_loss, fused_optimizer=args.fused_optimizer)
+                    deterministic_update=args.deterministic_update, fused_loss=args.fused_loss, fused_optimizer=args.fused_optimizer, fused_norm=args.fused_norm)
     agent = AgentPPO(env, cfg, seed=0)
     ts, tu, n = 0.0, 0.0, 0
     for ep in range(args.epochs):
