@@ -209,6 +209,17 @@ def intervaled_frame(times, length, num_frames, dt):
     return ((1.0 - blend) * idx0 + blend * idx1).astype(np.int64)
 
 
+def resample(rand, cdf32, lengths32, truncate):
+    """MotionLibBase.sample_motions + sample_time (:277-292) as the device states them, in float32: rand [N,2] uniform draws,
+    cdf32 [M] the float32 CDF of the batch sampling probabilities, lengths32 [M].  Clip = the first one whose CDF entry exceeds
+    rand[:,0] (the last clip if none does), start time = rand[:,1] * max(length - truncate, 0).  One comparison, one
+    subtraction and one product per output, each rounded once: a float32 restatement has exactly one answer."""
+    rand, cdf32, lengths32 = np.asarray(rand, np.float32), np.asarray(cdf32, np.float32), np.asarray(lengths32, np.float32)
+    ids = np.minimum(np.searchsorted(cdf32, rand[:, 0], side="right"), len(cdf32) - 1)
+    span = np.maximum(lengths32[ids] - np.float32(truncate), np.float32(0))
+    return ids.astype(np.int32), (rand[:, 1] * span).astype(np.float32)
+
+
 # ---------------------------------------------------------------- imitation task (PHC formulation; not in the reference)
 def quat_rotate(q, v):
     w, qv = q[..., :1], q[..., 1:]

@@ -267,7 +267,11 @@ SS_DEV int frame_intervaled(const ss_motion_data &d, int id, float time) {
   const float phase = clampf(time / len, 0.f, 1.f), tm = time < 0.f ? 0.f : time;
   const float i0 = phase * (float)(nf - 1), i1 = fminf(i0 + 1.f, (float)(nf - 1));
   const float b = clampf((tm - i0 * dt) / dt, 0.f, 1.f);
-  return s0 + (int)((1.f - b) * i0 + b * i1);
+  // the reference's (1 - b) i0 + b i1, written so that past the clip end, where i0 = i1 = nf - 1, the value is that integer
+  // whatever b is: there the two rounded products can add up to just below it (0.7499999 * 13 + 0.2500001 * 13 = 12.999999 in
+  // float32, the b that the device's contracted time - i0 * dt gives 0.25 dt past a 14-frame clip), and the cast then picked
+  // the frame before the last
+  return s0 + (int)(i0 + b * (i1 - i0));
 }
 // torch_utils.slerp (smpl_sim/utils/torch_utils.py:405-426)
 SS_DEV Q slerp(const Q &q0, Q q1, float t) {

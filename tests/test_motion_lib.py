@@ -1,5 +1,6 @@
 """Motion library (BASELINE config 4): oracle vs the reference's golden vectors, and the kernel source
-(ss_motion.h, run on the CPU emulator) vs both.  GPU twins of the kernel tests live in test_gpu_parity.py.
+(ss_motion.h, run on the CPU emulator) vs both.  GPU twins of the kernel tests live in test_gpu_parity.py; the kernels'
+clip, tile and blend edges are in motion_edge_cases.py, run by test_motion_edges_emu.py and test_motion_edges_gpu.py.
 
 Tolerances: everything is float32 arithmetic on both sides.  Positions / quaternions / Euler angles 2e-5 absolute;
 linear velocities 2e-3 (differences of float32 positions divided by dt <= 1/30); angular velocities 5e-2 rad/s
@@ -169,54 +170,84 @@ def random_sim_state(rs, n, J):
     return pos, q, vel
 
 
-def check_imitation(lib, clib, rs, n=37, device="cpu", stream=None):
+def check_imitation(lib, clib, rs, n=37, device="cpu", stream=None, cur_t=None, case=None):
+    """ss_imitation_step against the float64 oracle: observation 2e-4, reward and its parts 2e-5, both flags, then a masked
+    launch with a row stride.
+    cur_t: optional int32 [n] control-step counters handed to the kernel; the clip time is then start + cur_t * obs_dt.
+    case: optional dict(ids, times, exact, dist) in place of the random draw of clips and start times (tests/motion_edge_cases.py):
+    envs with exact[i] carry the clip's own state at their time, envs with a finite dist[i] have every body at that distance
+    from its reference body; no env is moved far off and none is excluded from the termination check, and the two assertions
+    about the spread of the random population do not apply.  Returns the inputs, outputs and a launch function."""
     import ctypes as C
     from smplsim_amd import _cabi
-    J = 24
-    ids = rs.integers(0, lib.num_current_motions(), size=n).astype(np.int32)
-    times = (rs.uniform(0, 0.9, size=n) * lib._motion_lengths[ids]).astype(np.float32)
+    J = lib.skeleton.num_joints
+    dt = np.float32(1.0 / 30)
+    if case is None:
+        ids = rs.integers(0, lib.num_current_motions(), size=n).astype(np.int32)
+        times = (rs.uniform(0, 0.9, size=n) * lib._motion_lengths[ids]).astype(np.float32)
+    else:
+        ids, times = np.asarray(case["ids"], np.int32), np.asarray(case["times"], np.float32)
     off = rs.normal(size=(n, 3)).astype(np.float32) * 0.1
-    # simulated humanoid = reference pose at `times` + noise, so that every reward term is in its sensitive range
-    ref = mo.motion_state(lib_arrays(lib), ids, times.astype(np.float64), off.astype(np.float64))
+    now = times if cur_t is None else (times + np.asarray(cur_t).astype(np.float32) * dt).astype(np.float32)
+    # simulated humanoid = reference pose at `now` + noise, so that every reward term is in its sensitive range
+    ref = mo.motion_state(lib_arrays(lib), ids, now.astype(np.float64), off.astype(np.float64))
     pos = ref["rg_pos"] + rs.normal(size=(n, J, 3)) * 0.05
     dq = mo.axis_angle_to_quaternion(rs.normal(size=(n, J, 3)) * 0.2)
     quat = mo.quat_mul(dq, ref["rb_rot"])
     vel = np.concatenate([ref["body_vel"] + rs.normal(size=(n, J, 3)), ref["body_ang_vel"] + rs.normal(size=(n, J, 3))], -1)
-    pos[: n // 4] += rs.normal(size=(n // 4, 1, 3)) * 0.4          # some envs far off: termination
+    if case is None:
+        pos[: n // 4] += rs.normal(size=(n // 4, 1, 3)) * 0.4          # some envs far off: termination
+    else:
+        u = rs.normal(size=(n, J, 3))
+        u /= np.linalg.norm(u, axis=-1, keepdims=True)
+        for i in range(n):
+            if np.isfinite(case["dist"][i]):
+                pos[i] = ref["rg_pos"][i] + u[i] * case["dist"][i]
+            if case["exact"][i]:
+                pos[i], quat[i] = ref["rg_pos"][i], ref["rb_rot"][i]
+                vel[i] = np.concatenate([ref["body_vel"][i], ref["body_ang_vel"][i]], -1)
     xmat = mo.quaternion_to_matrix(quat).reshape(n, J, 9)
     cfg = _cabi.ImitationCfg(100.0, 10.0, 0.1, 0.1, 0.5, 0.3, 0.1, 0.1, 0.25, 1.0 / 30)
     t = lambda a, dt=torch.float32: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(device)  # noqa: E731
     d_ids, d_times, d_off, d_pos, d_mat, d_vel = t(ids, torch.int32), t(times), t(off), t(pos), t(xmat), t(vel)
+    d_cur = None if cur_t is None else t(cur_t, torch.int32)
     obs = torch.zeros(n, 24 * J, device=device); rew = torch.zeros(n, device=device); parts = torch.zeros(n, 4, device=device)
     term = torch.zeros(n, dtype=torch.uint8, device=device)
-    p = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
+    p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
     trunc = torch.zeros(n, dtype=torch.uint8, device=device)
-    rc = clib.ss_imitation_step(C.byref(lib.data), C.byref(cfg), p(d_ids), p(d_times), None, p(d_off), None, n, p(d_pos), p(d_mat), p(d_vel),
-                                p(obs), 24 * J, p(rew), p(parts), p(term), p(trunc), stream)
-    assert rc == 0, clib.ss_last_error()
-    if device != "cpu":
-        torch.cuda.synchronize()
-    nxt = mo.motion_state(lib_arrays(lib), ids, (times + np.float32(1.0 / 30)).astype(np.float64), off.astype(np.float64))
+
+    def launch(obs_ptr, stride, rew, parts, term, trunc, mask=None):
+        rc = clib.ss_imitation_step(C.byref(lib.data), C.byref(cfg), p(d_ids), p(d_times), p(d_cur), p(d_off), p(mask), n, p(d_pos), p(d_mat),
+                                    p(d_vel), obs_ptr, stride, p(rew), p(parts), p(term), p(trunc), stream)
+        assert rc == 0, clib.ss_last_error()
+        if device != "cpu":
+            torch.cuda.synchronize()
+
+    launch(p(obs), 24 * J, rew, parts, term, trunc)
+    nxt = mo.motion_state(lib_arrays(lib), ids, (now + dt).astype(np.float64), off.astype(np.float64))
     want_obs = mo.imitation_obs(pos, quat, vel[..., :3], vel[..., 3:], nxt["rg_pos"], nxt["rb_rot"], nxt["body_vel"], nxt["body_ang_vel"])
     want_rew, want_parts = mo.imitation_reward(pos, quat, vel[..., :3], vel[..., 3:], ref["rg_pos"], ref["rb_rot"], ref["body_vel"], ref["body_ang_vel"])
     want_term = mo.imitation_reset(pos, ref["rg_pos"], 0.25)
-    assert np.abs(obs.cpu().numpy() - want_obs).max() < 2e-4
-    assert np.abs(parts.cpu().numpy() - want_parts).max() < 2e-5
-    assert np.abs(rew.cpu().numpy() - want_rew).max() < 2e-5
-    assert want_parts.min() < 0.5 < want_parts.max()
-    margin = np.abs(np.linalg.norm(pos - ref["rg_pos"], axis=-1).mean(-1) - 0.25) > 1e-4
-    assert (term.cpu().numpy().astype(bool) == want_term)[margin].all() and want_term.any() and not want_term.all()
-    assert np.array_equal(trunc.cpu().numpy().astype(bool), times + np.float32(1.0 / 30) >= lib._motion_lengths[ids])
+    err = dict(obs=np.abs(obs.cpu().numpy() - want_obs).max(), parts=np.abs(parts.cpu().numpy() - want_parts).max(),
+               reward=np.abs(rew.cpu().numpy() - want_rew).max())
+    assert err["obs"] < 2e-4, err
+    assert err["parts"] < 2e-5, err
+    assert err["reward"] < 2e-5, err
+    if case is None:
+        assert want_parts.min() < 0.5 < want_parts.max()
+        margin = np.abs(np.linalg.norm(pos - ref["rg_pos"], axis=-1).mean(-1) - 0.25) > 1e-4
+        assert (term.cpu().numpy().astype(bool) == want_term)[margin].all() and want_term.any() and not want_term.all()
+    else:
+        assert np.array_equal(term.cpu().numpy().astype(bool), want_term)
+    assert np.array_equal(trunc.cpu().numpy().astype(bool), now + dt >= lib._motion_lengths[ids])
     # masked launch with a row stride: only the selected envs' observation rows are written, nothing else
     mask = torch.as_tensor((np.arange(n) % 3 == 0).astype(np.uint8)).to(device)
     wide = torch.full((n, 24 * J + 7), -5.0, device=device)
-    rc = clib.ss_imitation_step(C.byref(lib.data), C.byref(cfg), p(d_ids), p(d_times), None, p(d_off), p(mask), n, p(d_pos), p(d_mat), p(d_vel),
-                                C.c_void_p(wide.data_ptr() + 4 * 7), 24 * J + 7, None, None, None, None, stream)
-    assert rc == 0
-    if device != "cpu":
-        torch.cuda.synchronize()
+    launch(C.c_void_p(wide.data_ptr() + 4 * 7), 24 * J + 7, None, None, None, None, mask)
     wide, mk = wide.cpu().numpy(), mask.cpu().numpy().astype(bool)
     assert (wide[:, :7] == -5.0).all() and (wide[~mk] == -5.0).all() and np.array_equal(wide[mk][:, 7:], obs.cpu().numpy()[mk])
+    return dict(launch=launch, ptr=p, now=now, ids=ids, obs=obs, reward=rew, parts=parts, terminated=term, truncated=trunc,
+                want_parts=want_parts, want_term=want_term, err=err)
 
 
 def test_emu_imitation_step_matches_oracle(emu_lib):
