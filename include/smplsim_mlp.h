@@ -210,6 +210,35 @@ int64_t ss_running_norm_workspace(int32_t M, int32_t dim);
 int ss_running_norm_update(const float *x, int32_t M, int32_t dim, int32_t ldx, float *mean, float *var, float *std, int64_t *n, void *workspace,
                            int64_t workspace_bytes, void *stream);
 
+/* ss_gather_rows: the shuffle of a mini-batch epoch of the update (the reference's agents/agent_ppo.py:26-46: states[perm].clone(), ... for seven tensors, then a
+ * slice per mini-batch) — the rows perm[i] of up to 8 tensors copied into a blocked layout by ONE launch, so that every block of every tensor is a view the network
+ * passes take as it is (learning/minibatch.py).
+ *   result    for i in [0, rows) and every tensor: dst row (i / block_rows) * dst_block_stride + i % block_rows, columns [0, cols), equals src row perm[i], byte for
+ *             byte.  No value is interpreted: NaN payloads and bf16 bit patterns survive.
+ *   untouched everything else in dst: the columns >= cols, the dst_block_stride - block_rows rows between two blocks, the rows after the last block (the owner
+ *             zeroes them once: the pad rows of a bf16 operand).
+ *   perm      [rows] int64 on the device.  An entry outside [0, src_rows) skips row i in every tensor: its dst row keeps what it held and no other row is affected;
+ *             the kernel compares the entry with the range before it forms an address from it.  Entries may repeat.
+ *   tensors   a HOST array of `count` descriptors, 1 <= count <= 8; it is copied into the kernel arguments and may be freed on return.
+ *             src   [src_rows, ld_src] elements of elem_bytes bytes (2 or 4), unit column stride; not modified.
+ *             dst   blocked as above, row stride ld_dst elements; ld_src, ld_dst >= cols, in elements; dst_block_stride >= block_rows, in dst rows.
+ *   overlap   the bytes a call reads ([src, src + ((src_rows - 1) ld_src + cols) elem_bytes) of every tensor, and perm) and the bytes it writes must not overlap —
+ *             not within a tensor (refused, src == dst included) and not between two tensors of a call (not checked).
+ *   access    per tensor, 16-byte loads and stores where both bases, ld_src * elem_bytes, ld_dst * elem_bytes and cols * elem_bytes are multiples of 16; else 4-byte
+ *             ones where they are multiples of 4; else element by element.  The three paths give the same bytes.  A row of u such units is served by
+ *             min(64, next power of two >= u) neighbouring lanes: a one-column tensor takes one thread per row, not one wavefront.
+ * One launch on `stream`, no workspace, no atomics, no host synchronisation, nothing read back.  SS_ERR_INVALID, nothing launched: a null tensors, perm, src or dst;
+ * count outside [1, 8]; elem_bytes not 2 or 4; cols < 1; ld_src or ld_dst < cols; dst_block_stride < block_rows; src_rows, rows or block_rows < 1; a base not
+ * aligned to elem_bytes (perm: to 8 bytes); src and dst of a tensor overlapping; more than 2^31 - 1 workgroups. */
+typedef struct ss_gather_tensor {
+  const void *src;
+  void *dst;
+  int32_t elem_bytes;
+  int32_t cols, ld_src, ld_dst;
+  int32_t dst_block_stride;
+} ss_gather_tensor;
+int ss_gather_rows(const ss_gather_tensor *tensors, int32_t count, const int64_t *perm, int32_t src_rows, int32_t rows, int32_t block_rows, void *stream);
+
 /* Test hook: the GEMM instantiation launched last by an ss_linear_* / ss_wgrad_bf16* call on the calling host thread, as
  * "<family> mode=<G256 mode or -> bn=<BN> bk=<BK> waves=<waves per workgroup> out=<bf16|f32|f32acc|f32det> ksplit=<K shares> kper=<K tiles per share>"
  * with family linear / glds / train / gemm256 / wgrad (empty before the first launch).  The deterministic entries report their GEMM, not their reduce pass:

@@ -145,7 +145,7 @@ ACTIVATIONS = {"none": 0, "silu": 1, "tanh": 2, "relu": 3}
 MLP_EXPORTS = ["ss_linear_bf16", "ss_linear_bf16_train", "ss_linear_bf16_dx", "ss_wgrad_bf16", "ss_obs_to_bf16", "ss_gaussian_sample",
                "ss_debug_last_gemm", "ss_linear_bf16_dx_det", "ss_linear_bf16_dx_det_workspace", "ss_wgrad_bf16_det", "ss_wgrad_bf16_det_workspace",
                "ss_ppo_policy_head", "ss_ppo_policy_head_workspace", "ss_value_head", "ss_value_head_workspace", "ss_adam_step", "ss_adam_step_workspace",
-               "ss_running_norm_update", "ss_running_norm_workspace"]            # include/smplsim_mlp.h (product library only: the matrix-core kernels)
+               "ss_running_norm_update", "ss_running_norm_workspace", "ss_gather_rows"]            # include/smplsim_mlp.h (product library only: the matrix-core kernels)
 
 
 class AdamTensor(C.Structure):
@@ -154,7 +154,14 @@ class AdamTensor(C.Structure):
                 ("rows", C.c_int32), ("cols", C.c_int32), ("ldg", C.c_int32), ("ld_w", C.c_int32), ("ld_wt", C.c_int32)]
 
 
+class GatherTensor(C.Structure):
+    """ss_gather_tensor of include/smplsim_mlp.h: one tensor of an ss_gather_rows call."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("elem_bytes", C.c_int32), ("cols", C.c_int32), ("ld_src", C.c_int32), ("ld_dst", C.c_int32),
+                ("dst_block_stride", C.c_int32)]
+
+
 ADAM_MAX_TENSORS = 32            # tensors of one ss_adam_step call (the table travels in the kernel arguments)
+GATHER_MAX_TENSORS = 8           # tensors of one ss_gather_rows call
 NORM_BLOCK_ROWS = 256            # SS_NORM_BLOCK_ROWS: rows per (mean, M2) pair in the workspace of ss_running_norm_update
 
 
@@ -183,6 +190,8 @@ def bind_mlp(lib):
     # (x, M, dim, ldx, mean, var, std, n, workspace, bytes, stream)
     lib.ss_running_norm_update.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int64, vp]
     lib.ss_running_norm_workspace.argtypes = [C.c_int32, C.c_int32]; lib.ss_running_norm_workspace.restype = C.c_int64
+    # (tensors, count, perm, src_rows, rows, block_rows, stream)
+    lib.ss_gather_rows.argtypes = [C.POINTER(GatherTensor), C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp]
     return lib
 
 

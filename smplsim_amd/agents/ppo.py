@@ -4,7 +4,8 @@ What it replaces in the reference: Agent.sample (agents/agent.py:64-145: up to 3
 pickled Memory objects), the Python GAE loop (learning_utils.py:198-218) and AgentPPO.update_policy
 (agents/agent_ppo.py:20-99) — keeping their semantics (sampling from the Gaussian policy with eval-mode normalisation,
 obs clipping to clip_obs_range, actions clipped to the action space before they reach the env while the unclipped
-sample is what is stored, full-batch epochs of one critic step + one clipped-surrogate step, grad-norm clipping,
+sample is what is stored, full-batch epochs of one critic step + one clipped-surrogate step — or, with use_mini_batch, the mini-batch
+epochs of agent_ppo.py:26-46 over a batch shuffled on the device (learning/minibatch.py) —, grad-norm clipping,
 the checkpoint dictionary layout of agent_humanoid.py:115-140).
 
 What is different by construction: N envs advance in lock step for a fixed horizon T instead of every worker finishing
@@ -51,6 +52,8 @@ class PPOConfig:
     fused_loss: bool = False       # update: surrogate, value loss and their gradients by the library's loss heads (learning/fused_loss.py), whichever path ran the networks
     fused_optimizer: bool = False  # update: gradient clipping and Adam by the library's optimiser step (learning/fused_optim.py); with mfma_update it also keeps the bf16 weight images current
     fused_norm: bool = False       # with mfma_update: the policy's train-mode RunningNorm by the library's kernels (learning/fused_norm.py) and the networks' bf16 inputs made once, not once per pass
+    use_mini_batch: bool = False   # update: mini-batch epochs (agent_ppo.py:26-46): per epoch a permutation of the batch and floor(M / mini_batch_size) iterations of one critic step + one policy step
+    mini_batch_size: int = 0       # rows per mini-batch (with use_mini_batch: >= 1, and at most the rollout's rows at update time)
     extra: dict = field(default_factory=dict)
 
 
@@ -69,9 +72,19 @@ class AgentPPO:
             raise ValueError("fused_norm applies to the mfma_update path only (it hands the networks' passes their bf16 operands)")
         if c.fused_norm and self.device.type != "cuda":
             raise RuntimeError("fused_norm needs the env on a GPU (the RunningNorm kernels have no CPU path)")
+        if c.use_mini_batch and c.mini_batch_size < 1:
+            raise ValueError("use_mini_batch needs mini_batch_size >= 1")
+        if c.extra.get("minibatch_gather", "kernel") not in ("kernel", "torch"):
+            raise ValueError("extra['minibatch_gather'] is 'kernel' (ss_gather_rows) or 'torch'")
         torch.manual_seed(seed)
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed)
+        self.gen_update = None
+        if c.use_mini_batch:
+            # the epochs' permutations: a generator of its own, so that the sampler's draws (self.gen, torch's global one) are those of an agent without the flag
+            self.gen_update = torch.Generator(device=self.device)
+            self.gen_update.manual_seed(seed + 0x5EED)
+        self._shuffled = None
         self.state_dim, self.action_dim = env.obs_size, env.nu
         self.policy_net = PolicyGaussian(self.state_dim, self.action_dim, c.hidden, c.activation, c.log_std, c.fix_std).to(self.device)
         self.value_net = Value(MLP(self.state_dim, c.hidden, c.activation)).to(self.device)
@@ -285,8 +298,69 @@ class AgentPPO:
             self.optimizer_value.step()
         return loss.detach()
 
-    def update_params(self, batch):
+    def _policy_step(self, s, a, adv, flp):
         c = self.cfg
+        loss = self.ppo_loss(s, a, adv, flp)
+        self.optimizer_policy.zero_grad(set_to_none=True)
+        loss.backward()
+        if c.policy_grad_clip is not None and not c.fused_optimizer:      # (fused_optimizer: inside the step)
+            torch.nn.utils.clip_grad_norm_(self.policy_net.parameters(), c.policy_grad_clip)
+        self.optimizer_policy.step()
+        return loss.detach()
+
+    def _mini_batch_epochs(self, states, critic_states, actions, adv, ret, fixed_log_probs, exps, perms, info):
+        """agent_ppo.py:26-46 over a batch shuffled on the device.  Per epoch: a permutation of all M rows, then floor(M / B) iterations over consecutive slices of
+        the shuffled batch (the last M mod B rows sit the epoch out), each one update_value on all rows of the slice and one policy step on its exploration rows.
+        Epoch e takes perms[e] as the order of the ORIGINAL batch (the reference shuffles the shuffled batch again: the same distribution of orders).  The whole
+        batch goes into its order by one ShuffledBatch.shuffle per epoch, and an iteration works on views of it: no host synchronisation per iteration.
+        mini_batch_size > M is refused: the reference would silently take zero steps."""
+        c = self.cfg
+        M, B, E = states.shape[0], c.mini_batch_size, c.opt_num_epochs
+        if B > M:
+            raise ValueError(f"mini_batch_size = {B} exceeds the rollout's {M} rows: an epoch would take no step")
+        if perms is not None:
+            if not torch.is_tensor(perms) or perms.dtype != torch.int64 or tuple(perms.shape) != (E, M) or perms.device != states.device:
+                raise ValueError(f"perms must be an int64 [{E}, {M}] tensor on {states.device}")
+            if int(perms.min()) < 0 or int(perms.max()) >= M:
+                raise ValueError(f"perms holds a row outside [0, {M})")
+        # ONE reduction per update (the full-batch path pays a nonzero): sample() marks every row as an exploration row, and then no iteration indexes anything
+        all_exps = bool((exps != 0).all())
+        if not all_exps and self.fused_policy is not None:
+            raise ValueError("use_mini_batch with mfma_update needs every row to be an exploration row (exps all non-zero): a row count that varies from "
+                             "mini-batch to mini-batch would grow FusedMLPTrain's per-shape buffers without bound")
+        sources = dict(states=states, actions=actions, adv=adv, ret=ret, flp=fixed_log_probs)
+        if not all_exps:
+            sources["exps"] = exps.reshape(M, 1)
+        if c.fused_norm:
+            sources["critic"] = critic_states                   # the critic's bf16 operand, cast once per update: gathered as bf16, not cast again
+        mode = "torch" if self.device.type != "cuda" else c.extra.get("minibatch_gather", "kernel")
+        if self._shuffled is not None and self._shuffled.matches(sources, B, mode):
+            self._shuffled.bind(sources)
+        else:
+            from ..learning.minibatch import ShuffledBatch
+            self._shuffled = ShuffledBatch(sources, B, mode)
+        sb = self._shuffled
+        steps = 0
+        for e in range(E):
+            perm = perms[e] if perms is not None else torch.randperm(M, generator=self.gen_update, device=self.device)
+            sb.shuffle(perm)
+            for i in range(sb.num_blocks):
+                blk = sb.block(i)
+                info["value_loss"] = self.update_value(blk["critic"] if c.fused_norm else blk["states"], blk["ret"])
+                s, a, ad, flp = blk["states"], blk["actions"], blk["adv"], blk["flp"]
+                if not all_exps:
+                    ind = blk["exps"].reshape(-1).nonzero(as_tuple=False).squeeze(1)
+                    s, a, ad, flp = s[ind], a[ind], ad[ind], flp[ind]
+                info["surr_loss"] = self._policy_step(s, a, ad, flp)
+                steps += 1
+        return steps
+
+    def update_params(self, batch, perms=None):
+        """perms (use_mini_batch only): an int64 [opt_num_epochs, M] device tensor, row e the order of epoch e — for tests and replay; by default the orders come
+        from torch.randperm on the agent's own update generator."""
+        c = self.cfg
+        if perms is not None and not c.use_mini_batch:
+            raise ValueError("perms applies to use_mini_batch only")
         T, N = batch["rewards"].shape
         states = batch["states"].reshape(T * N, -1)
         self.policy_net.eval(); self.value_net.eval()
@@ -302,24 +376,23 @@ class AgentPPO:
         adv = normalize_advantages(adv).reshape(T * N, 1)
         ret = ret.reshape(T * N, 1)
         actions = batch["actions"].reshape(T * N, -1)
-        ind = batch["exps"].reshape(-1).nonzero(as_tuple=False).squeeze(1)
         if "log_probs" in batch:                               # sampled by the bf16 inference path: its own log-densities
             fixed_log_probs = batch["log_probs"].reshape(T * N, 1)
         else:
             with torch.no_grad(), self._autocast():
                 fixed_log_probs = self._f32(self.policy_net.get_log_prob(states, actions))
         self.policy_net.train(); self.value_net.train()        # RunningNorm statistics follow the training passes
-        s_i, a_i, adv_i, flp_i = states[ind], actions[ind], adv[ind], fixed_log_probs[ind]
         info = {}
-        for _ in range(c.opt_num_epochs):
-            info["value_loss"] = self.update_value(critic_states, ret)
-            loss = self.ppo_loss(s_i, a_i, adv_i, flp_i)
-            self.optimizer_policy.zero_grad(set_to_none=True)
-            loss.backward()
-            if c.policy_grad_clip is not None and not c.fused_optimizer:      # (fused_optimizer: inside the step)
-                torch.nn.utils.clip_grad_norm_(self.policy_net.parameters(), c.policy_grad_clip)
-            self.optimizer_policy.step()
-            info["surr_loss"] = loss.detach()
+        if c.use_mini_batch:
+            steps = self._mini_batch_epochs(states, critic_states, actions, adv, ret, fixed_log_probs, batch["exps"].reshape(-1), perms, info)
+        else:
+            ind = batch["exps"].reshape(-1).nonzero(as_tuple=False).squeeze(1)
+            s_i, a_i, adv_i, flp_i = states[ind], actions[ind], adv[ind], fixed_log_probs[ind]
+            for _ in range(c.opt_num_epochs):
+                info["value_loss"] = self.update_value(critic_states, ret)
+                info["surr_loss"] = self._policy_step(s_i, a_i, adv_i, flp_i)
+            steps = c.opt_num_epochs
+        info["opt_steps"] = torch.tensor(steps)                # (a tensor like every other value of info; on the host: it was counted there)
         stats = getattr(getattr(self, "surrogate", None), "last_stats", None)
         if stats is not None:
             info["clip_frac"], info["approx_kl"] = stats[1], stats[2]   # of the last iteration, from the head's launch

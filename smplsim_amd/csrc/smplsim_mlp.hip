@@ -29,6 +29,7 @@
 #include "ss_ppo_head.h"
 #include "ss_optim.h"
 #include "ss_norm.h"
+#include "ss_gather.h"
 
 namespace {
 
@@ -1347,6 +1348,47 @@ int ss_running_norm_update(const float *x, int32_t M, int32_t dim, int32_t ldx, 
   hipLaunchKernelGGL(run_norm::ss_norm_partials_kernel, dim3((unsigned)(P * groups)), dim3(256), 0, st, x, M, dim, ldx, (int)groups, part);
   hipLaunchKernelGGL(run_norm::ss_norm_merge_kernel, dim3(1), dim3(256), 0, st, static_cast<const double *>(part), (int)P, M, dim, mean, var, sd,
                      reinterpret_cast<long long *>(n));
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
+}
+
+// ---- the rows of a mini-batch epoch (ss_gather.h): one launch on `stream` for all tensors, the descriptor table by value in the kernel arguments
+int ss_gather_rows(const ss_gather_tensor *tensors, int32_t count, const int64_t *perm, int32_t src_rows, int32_t rows, int32_t block_rows, void *stream) {
+  if (!tensors || !perm) return fail(SS_ERR_INVALID, "null argument");
+  if (count < 1 || count > gather::MAX_TENSORS) return fail(SS_ERR_INVALID, "ss_gather_rows: 1 <= count <= 8 tensors in one call");
+  if (src_rows < 1 || rows < 1 || block_rows < 1) return fail(SS_ERR_INVALID, "ss_gather_rows: src_rows >= 1, rows >= 1, block_rows >= 1");
+  if (reinterpret_cast<size_t>(perm) & 7) return fail(SS_ERR_INVALID, "ss_gather_rows: perm must be 8-byte aligned");
+  gather::Table tb{};
+  int64_t tiles = 0;
+  const int64_t last = (int64_t)(rows - 1) / block_rows, last_in = (int64_t)(rows - 1) % block_rows;
+  for (int i = 0; i < count; i++) {
+    const ss_gather_tensor &d = tensors[i];
+    if (!d.src || !d.dst) return fail(SS_ERR_INVALID, "null argument");
+    if (d.elem_bytes != 2 && d.elem_bytes != 4) return fail(SS_ERR_INVALID, "ss_gather_rows: elem_bytes must be 2 or 4");
+    if (d.cols < 1) return fail(SS_ERR_INVALID, "ss_gather_rows: cols >= 1");
+    if (d.ld_src < d.cols || d.ld_dst < d.cols) return fail(SS_ERR_INVALID, "ss_gather_rows: row strides must be >= cols");
+    if (d.dst_block_stride < block_rows) return fail(SS_ERR_INVALID, "ss_gather_rows: dst_block_stride >= block_rows");
+    const size_t s = reinterpret_cast<size_t>(d.src), t = reinterpret_cast<size_t>(d.dst), eb = (size_t)d.elem_bytes;
+    if ((s | t) & (eb - 1)) return fail(SS_ERR_INVALID, "ss_gather_rows: src and dst must be aligned to elem_bytes");
+    // the bytes the call may read and those it may write must not meet (src == dst is the simplest case)
+    const size_t s_end = s + (((size_t)src_rows - 1) * d.ld_src + d.cols) * eb;
+    const size_t t_end = t + (((size_t)last * d.dst_block_stride + last_in) * d.ld_dst + d.cols) * eb;
+    if (s < t_end && t < s_end) return fail(SS_ERR_INVALID, "ss_gather_rows: src and dst must not overlap");
+    const size_t lds = (size_t)d.ld_src * eb, ldd = (size_t)d.ld_dst * eb, width = (size_t)d.cols * eb, all = s | t | lds | ldd | width;
+    const int unit = !(all & 15) ? 16 : !(all & 3) ? 4 : (int)eb;
+    const int upr = (int)(width / unit);
+    int l2 = 0;
+    while (l2 < 6 && (1 << l2) < upr) l2++;
+    const int per_row = (upr + (1 << l2) - 1) >> l2;                       // units a lane moves per row
+    const int tile_rows = (gather::THREADS >> l2) * gather::ROWS_IN_FLIGHT * (per_row == 1 ? 2 : 1);
+    tb.t[i] = gather::Tensor{static_cast<const char *>(d.src), static_cast<char *>(d.dst), (long long)lds, (long long)ldd, upr, unit, l2, tile_rows,
+                             d.dst_block_stride, (int)tiles};
+    tiles += row_groups(rows, tile_rows);
+    if (tiles > INT32_MAX) return fail(SS_ERR_INVALID, "ss_gather_rows: more than 2^31 - 1 workgroups in one call");
+  }
+  tb.count = count;
+  hipLaunchKernelGGL(gather::ss_gather_rows_kernel, dim3((unsigned)tiles), dim3(gather::THREADS), 0, (hipStream_t)stream, tb,
+                     reinterpret_cast<const long long *>(perm), src_rows, rows, block_rows);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? SS_OK : fail(SS_ERR_HIP, hipGetErrorString(e));
 }

@@ -5,6 +5,7 @@
 
     python tools/train_ppo.py --task HumanoidSpeed --envs 4096 --epochs 5
     python tools/train_ppo.py --task HumanoidIm --envs 2048 --epochs 30      # motion imitation (synthetic clips unless --motion-file)
+    python tools/train_ppo.py --task HumanoidIm --envs 2048 --mini-batch-size 8192   # six optimiser steps per epoch of the update instead of one
 """
 import argparse
 import json
@@ -34,6 +35,7 @@ def main():
     ap.add_argument("--fused-loss", action="store_true", help="update: surrogate, value loss and their gradients by the library's loss heads (adds clip_frac and approx_kl to the log line)")
     ap.add_argument("--fused-optimizer", action="store_true", help="update: gradient clipping and Adam by the library's optimiser step (learning/fused_optim.py; adds grad_norm to the log line)")
     ap.add_argument("--fused-norm", action="store_true", help="with --mfma-update: the policy's train-mode RunningNorm by the library's kernels and the networks' bf16 inputs made once (learning/fused_norm.py)")
+    ap.add_argument("--mini-batch-size", type=int, default=0, help="update: mini-batch epochs of this many rows, the batch shuffled on the device once per epoch (0 = full-batch epochs; adds opt_steps to the log line)")
     ap.add_argument("--save", default="")
     ap.add_argument("--log-every", type=int, default=1)
     ap.add_argument("--motion-file", default="", help="HumanoidIm: AMASS-style pickle ({key: {pose_aa, trans, fps}}); default = synthetic clips")
@@ -55,7 +57,8 @@ def main():
     else:
         env = SMPLSimVecEnv(args.envs, task=args.task, autoreset=True, seed=0)
     cfg = PPOConfig(hidden=tuple(int(x) for x in args.hidden.split(",")), min_batch_size=args.min_batch_size, opt_num_epochs=args.opt_epochs, amp_bf16=args.amp_bf16, mfma_inference=args.mfma_inference, mfma_update=args.mfma_update,
-                    deterministic_update=args.deterministic_update, fused_loss=args.fused_loss, fused_optimizer=args.fused_optimizer, fused_norm=args.fused_norm)
+                    deterministic_update=args.deterministic_update, fused_loss=args.fused_loss, fused_optimizer=args.fused_optimizer, fused_norm=args.fused_norm,
+                    use_mini_batch=args.mini_batch_size > 0, mini_batch_size=args.mini_batch_size)
     agent = AgentPPO(env, cfg, seed=0)
     ts, tu, n = 0.0, 0.0, 0
     for ep in range(args.epochs):
