@@ -1,6 +1,6 @@
-// ss_gemm256.h — K loop of the 256 x 256 macro-tile bf16 GEMM (y = x W^T, both operands K-contiguous) for gfx950, round 6.
+// ss_gemm256.h — K loops and kernel arguments of the 256 x 256 macro-tile bf16 GEMM (y = x W^T, both operands K-contiguous) for gfx950, round 6.
 //
-// Why another K loop: the 128 x BN kernels of smplsim_mlp.hip give a wave a 32 x BN/2 tile — 5 fragment reads per 4 matrix instructions, 87 FLOP
+// Why another K loop: the 128 x BN kernels of ss_gemm128.h give a wave a 32 x BN/2 tile — 5 fragment reads per 4 matrix instructions, 87 FLOP
 // per byte copied L2 -> LDS — and every wave of the workgroup reads, waits and multiplies in lockstep, so the matrix pipe idles while the
 // fragments arrive: 0.36-0.60 PFLOP/s on the PPO update's shapes (53 248 rows), half of hipBLASLt (profiles/r06_train_gemm_sweep.txt).
 // Here:
@@ -264,6 +264,43 @@ struct LoopTN {
     if (wr == 0) __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_s_barrier();
   }
+};
+
+// ---- arguments of the kernels (ss_gemm256_kernels.h; LinearTrainArgs also of ss_linear_train_kernel, ss_gemm128.h)
+struct LinearTrainArgs {
+  const __bf16 *X, *W;          // [M, K], [N, K] row-major, K a multiple of 64
+  const float *bias;            // [N] or null
+  const __bf16 *mul;            // [M, ldy] or null: the result is multiplied by it before the activation
+  void *Y;                      // [M, ldy] bf16 (or fp32 when f32_atomic: += partial sums; the caller zeroes it) or null
+  __bf16 *Yt;                   // [N, ldyt] transposed copy or null
+  __bf16 *Dact;                 // [M, ldy] act'(pre-activation) or null
+  int M, N, K, ldy, ldyt, act, xcd_remap;
+  alignas(8) int kper = 0;      // K tiles per share of the accumulating forms (the host's number; ss_gemm256_kernel: even); 0: the whole of K.  (aligned: kper and
+                                // colsum stay at the kernel-argument offsets 0x58 / 0x60 ss_gemm256_kernel was tuned at; packed, DXN and DXN_DET spill two more SGPRs)
+  float *colsum = nullptr;      // ss_gemm256_kernel with `mul`: [N] += column sums of the fp32 result (the bias gradient of the layer below);
+                                // G256_DXN_DET: the [2 * ceil(M / 256), N] partial column sums, stored
+};
+
+// ---- round 6, second GEMM of the update: 256 x 256 macro-tiles, the two wave rows one barrier apart (the K loop and the ordering
+// argument are above; the kernel is in ss_gemm256_kernels.h).  Arguments as ss_linear_train_kernel (ss_gemm128.h); the set of outputs is a template parameter:
+//     G256_ACCUM   fp32 partial sums of a K share added to Y by atomics (weight gradients)
+//     G256_PLAIN   Y = act(x W^T + b)
+//     G256_FWD     Y, Y^T and act'(pre-activation)                  (a hidden layer's forward pass)
+//     G256_DX      Y = (x W^T) * mul and Y^T                        (dZ of the layer below)
+//     G256_FWDN / G256_DXN   the same two without Y^T: since ss_wgrad_bf16 contracts over the ROWS of dZ and h, nothing needs a transposed copy
+// Why compile-time: the K loop alone runs the 53 248 x 1536 x 2048 product in 256 us = 1.31 PFLOP/s; the first epilogue (run-time `if (Y)`, `if (Dact)` per
+// element, one dependent exp -> rcp chain after the other between the branches, every 16-byte chunk of the output parked in scratch because its edge
+// path indexed it dynamically) cost 90 us for ONE image and 200 us for three (profiles/r06_gemm256.txt).
+enum { G256_ACCUM = 0, G256_PLAIN = 1, G256_FWD = 2, G256_DX = 3, G256_FWDN = 4, G256_DXN = 5,     // ..N: without the transposed image (ss_wgrad_bf16 reads the operands as they lie)
+       G256_DXN_DET = 6 };   // G256_DXN whose column sums are STORED, one row of partials per wave row (128 rows of the batch), instead of added to colsum (ss_linear_bf16_dx_det)
+
+// ---- round 6: the weight gradient from dZ and the layer's input AS THEY LIE (both [batch, features] row-major): dW[i][j] += sum_m dZ[m][i] h[m][j].  The forward and dX
+// products of the update are bound by what they WRITE (profiles/r06_gemm256.txt); with this kernel they need not write transposed copies any more.  K loop:
+// gemm256::LoopTN (fragments by ds_read_b64_tr_b16); K split over one round of the CUs, fp32 atomics, as ss_gemm256_kernel<G256_ACCUM>.
+struct WgradArgs {
+  const __bf16 *Z, *H;          // [Mb, ldz], [Mb, ldh]
+  float *dW;                    // [NI, ldw] += ; NI = columns of Z used, NJ = columns of H used (deterministic form: the workspace, ldw = NJ)
+  int NI, NJ, ldz, ldh, ldw, nkt, kper;
 };
 
 }  // namespace gemm256

@@ -1,4 +1,4 @@
-"""Every bf16 GEMM instantiation the host dispatch of smplsim_mlp.hip can launch, against a float64 reference on the device computed from
+"""Every bf16 GEMM instantiation (csrc/ss_gemm128.h, csrc/ss_gemm256_kernels.h) the host dispatch of smplsim_mlp.hip can launch, against a float64 reference on the device computed from
 the same bf16 operands, with an element-wise error bound derived from the arithmetic (not from max |ref|).  Each case asserts, through
 ss_debug_last_gemm, that it reached the instantiation it is meant to cover; sentinels around every output check that nothing is written
 outside the output's region; row strides that are not multiples of 8 and pointers offset by one element take the scalar epilogues.
