@@ -18,7 +18,6 @@ from dataclasses import dataclass, field
 
 import torch
 
-
 from ..learning.gae import estimate_advantages_columns, normalize_advantages
 from ..learning.networks import MLP, PolicyGaussian, Value
 
@@ -57,25 +56,31 @@ class PPOConfig:
     extra: dict = field(default_factory=dict)
 
 
+def _check_flags(c, device):
+    if c.deterministic_update and not c.mfma_update:
+        raise ValueError("deterministic_update applies to the mfma_update path only (the torch update paths are reproducible as they are)")
+    if c.fused_loss and device.type != "cuda":
+        raise RuntimeError("fused_loss needs the env on a GPU (the loss heads have no CPU path)")
+    if c.fused_optimizer and device.type != "cuda":
+        raise RuntimeError("fused_optimizer needs the env on a GPU (the optimiser step has no CPU path)")
+    if c.fused_norm and not c.mfma_update:
+        raise ValueError("fused_norm applies to the mfma_update path only (it hands the networks' passes their bf16 operands)")
+    if c.fused_norm and device.type != "cuda":
+        raise RuntimeError("fused_norm needs the env on a GPU (the RunningNorm kernels have no CPU path)")
+    if c.use_mini_batch and c.mini_batch_size < 1:
+        raise ValueError("use_mini_batch needs mini_batch_size >= 1")
+    if c.extra.get("minibatch_gather", "kernel") not in ("kernel", "torch"):
+        raise ValueError("extra['minibatch_gather'] is 'kernel' (ss_gather_rows) or 'torch'")
+
+
 class AgentPPO:
+    fast_policy = fused_policy = fused_value = lib_norm = surrogate = value_mse = _shuffled = None   # the optional parts: None = off (also on an object that __init__ never saw)
+
     def __init__(self, env, cfg=None, seed=0):
         self.env, self.cfg = env, cfg or PPOConfig()
         c = self.cfg
         self.device = env.device
-        if c.deterministic_update and not c.mfma_update:
-            raise ValueError("deterministic_update applies to the mfma_update path only (the torch update paths are reproducible as they are)")
-        if c.fused_loss and self.device.type != "cuda":
-            raise RuntimeError("fused_loss needs the env on a GPU (the loss heads have no CPU path)")
-        if c.fused_optimizer and self.device.type != "cuda":
-            raise RuntimeError("fused_optimizer needs the env on a GPU (the optimiser step has no CPU path)")
-        if c.fused_norm and not c.mfma_update:
-            raise ValueError("fused_norm applies to the mfma_update path only (it hands the networks' passes their bf16 operands)")
-        if c.fused_norm and self.device.type != "cuda":
-            raise RuntimeError("fused_norm needs the env on a GPU (the RunningNorm kernels have no CPU path)")
-        if c.use_mini_batch and c.mini_batch_size < 1:
-            raise ValueError("use_mini_batch needs mini_batch_size >= 1")
-        if c.extra.get("minibatch_gather", "kernel") not in ("kernel", "torch"):
-            raise ValueError("extra['minibatch_gather'] is 'kernel' (ss_gather_rows) or 'torch'")
+        _check_flags(c, self.device)
         torch.manual_seed(seed)
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed)
@@ -84,7 +89,6 @@ class AgentPPO:
             # the epochs' permutations: a generator of its own, so that the sampler's draws (self.gen, torch's global one) are those of an agent without the flag
             self.gen_update = torch.Generator(device=self.device)
             self.gen_update.manual_seed(seed + 0x5EED)
-        self._shuffled = None
         self.state_dim, self.action_dim = env.obs_size, env.nu
         self.policy_net = PolicyGaussian(self.state_dim, self.action_dim, c.hidden, c.activation, c.log_std, c.fix_std).to(self.device)
         self.value_net = Value(MLP(self.state_dim, c.hidden, c.activation)).to(self.device)
@@ -101,25 +105,21 @@ class AgentPPO:
         self.epoch, self.num_steps = 0, 0
         self.horizon = max(1, -(-c.min_batch_size // env.num_envs))
         self._obs = None
-        self.fast_policy = None
         if c.mfma_inference:
             from ..learning.fast_policy import FusedPolicyInference
             self.fast_policy = FusedPolicyInference(self.policy_net, c.clip_obs_range if c.clip_obs else None)
-        self.fused_policy = self.fused_value = None
         if c.mfma_update:
             from ..learning.fused_train import FusedMLPTrain
-            images = dict(weight_images=True) if c.fused_optimizer else {}      # the optimiser step writes the bf16 weight images the passes read
-            self.fused_policy = FusedMLPTrain(self.policy_net.net.affine_layers, self.policy_net.action_mean, c.activation, deterministic=c.deterministic_update, **images)
-            self.fused_value = FusedMLPTrain(self.value_net.net.affine_layers, self.value_net.value_head, c.activation, deterministic=c.deterministic_update, **images)
+            kw = dict(deterministic=c.deterministic_update, weight_images=c.fused_optimizer)   # (the optimiser step writes the bf16 weight images the passes read)
+            self.fused_policy = FusedMLPTrain(self.policy_net.net.affine_layers, self.policy_net.action_mean, c.activation, **kw)
+            self.fused_value = FusedMLPTrain(self.value_net.net.affine_layers, self.value_net.value_head, c.activation, **kw)
             if c.fused_optimizer:
                 for opt, net in ((self.optimizer_policy, self.fused_policy), (self.optimizer_value, self.fused_value)):
                     for w, wb, wt in net.images():
                         opt.attach_images(w, w_bf16=wb, wt_bf16=wt)
-        self.lib_norm = None
         if c.fused_norm:
             from ..learning.fused_norm import LibRunningNorm
             self.lib_norm = LibRunningNorm(self.policy_net.norm)
-        self.surrogate = self.value_mse = None
         if c.fused_loss:
             from ..learning.fused_loss import PPOSurrogate, ValueMSE
             self.surrogate, self.value_mse = PPOSurrogate(), ValueMSE()
@@ -251,35 +251,30 @@ class AgentPPO:
     def _policy_input(self, states):
         """What the policy's pass on the library's GEMM reads: RunningNorm(states) (train mode: its statistics follow the passes as in the torch path) — by torch as
         an fp32 tensor, or with fused_norm by the library's kernels as the pass's bf16 operand."""
-        lib_norm = getattr(self, "lib_norm", None)
-        return lib_norm(states) if lib_norm is not None else self.policy_net.norm(states)
+        return self.lib_norm(states) if self.lib_norm is not None else self.policy_net.norm(states)
 
-    def _policy_log_prob(self, states, actions):
-        """PolicyGaussian.get_log_prob with the network passes on the library's GEMM (mfma_update): RunningNorm (_policy_input), mean = head(MLP(.)), the
-        log-density in fp32 torch."""
-        p = self.policy_net
-        mean = self.fused_policy(self._policy_input(states))
-        log_std = p.action_log_std.expand_as(mean)
+    def _policy_log_prob(self, mean, actions):
+        """PolicyGaussian.get_log_prob of a mean that the library's GEMM made (mfma_update: ppo_loss): the log-density in fp32 torch."""
+        log_std = self.policy_net.action_log_std.expand_as(mean)
         z = (actions - mean) * torch.exp(-log_std)
         terms = -0.5 * z * z - log_std - 0.5 * math.log(2.0 * math.pi)
         # the row sums as a matrix-vector product: torch's reduction over the 69 columns of a [53 248, 69] tensor (and its backward) was 180 us a call
         return torch.matmul(terms, torch.ones(terms.shape[1], 1, dtype=terms.dtype, device=terms.device))
 
     def ppo_loss(self, states, actions, advantages, fixed_log_probs):
-        if getattr(self, "surrogate", None) is not None:
-            # fused_loss: the head's fp32 mean from whichever path runs the network; log-density, surrogate and both gradients in ss_ppo_policy_head
-            p = self.policy_net
-            if self.fused_policy is not None:
-                mean = self.fused_policy(self._policy_input(states))
-            else:
+        p = self.policy_net
+        mean = self.fused_policy(self._policy_input(states)) if self.fused_policy is not None else None   # the head's fp32 mean on the library's GEMM
+        if self.surrogate is not None:
+            # fused_loss: the mean from whichever path runs the network; log-density, surrogate and both gradients in ss_ppo_policy_head
+            if mean is None:
                 with self._autocast():
                     mean = self._f32(p.mean_and_log_std(states)[0])
             return self.surrogate(mean, p.action_log_std, actions, advantages, fixed_log_probs, self.cfg.clip_epsilon)
-        if getattr(self, "fused_policy", None) is not None:
-            log_probs = self._policy_log_prob(states, actions)
+        if mean is not None:
+            log_probs = self._policy_log_prob(mean, actions)
         else:
             with self._autocast():
-                log_probs = self._f32(self.policy_net.get_log_prob(states, actions))
+                log_probs = self._f32(p.get_log_prob(states, actions))
         ratio = torch.exp(log_probs - fixed_log_probs)
         clipped = ratio.clamp(1.0 - self.cfg.clip_epsilon, 1.0 + self.cfg.clip_epsilon)
         return -torch.minimum(ratio * advantages, clipped * advantages).mean()
@@ -287,12 +282,12 @@ class AgentPPO:
     def update_value(self, critic_states, returns):
         """critic_states: the fp32 states, or (fused_norm) the critic's Bf16Operand of them."""
         for _ in range(self.cfg.value_opt_niter):
-            if getattr(self, "fused_value", None) is not None:
+            if self.fused_value is not None:
                 pred = self.fused_value(critic_states)
             else:
                 with self._autocast():
                     pred = self._f32(self.value_net(critic_states))
-            loss = self.value_mse(pred, returns) if getattr(self, "value_mse", None) is not None else (pred - returns).pow(2).mean()
+            loss = self.value_mse(pred, returns) if self.value_mse is not None else (pred - returns).pow(2).mean()
             self.optimizer_value.zero_grad(set_to_none=True)
             loss.backward()
             self.optimizer_value.step()
@@ -326,8 +321,8 @@ class AgentPPO:
         # ONE reduction per update (the full-batch path pays a nonzero): sample() marks every row as an exploration row, and then no iteration indexes anything
         all_exps = bool((exps != 0).all())
         if not all_exps and self.fused_policy is not None:
-            raise ValueError("use_mini_batch with mfma_update needs every row to be an exploration row (exps all non-zero): a row count that varies from "
-                             "mini-batch to mini-batch would grow FusedMLPTrain's per-shape buffers without bound")
+            raise ValueError("use_mini_batch with mfma_update needs every row to be an exploration row (exps all non-zero): with a row count that varies from "
+                             "mini-batch to mini-batch every iteration would allocate and zero a new set of FusedMLPTrain's work tensors")
         sources = dict(states=states, actions=actions, adv=adv, ret=ret, flp=fixed_log_probs)
         if not all_exps:
             sources["exps"] = exps.reshape(M, 1)
@@ -367,7 +362,7 @@ class AgentPPO:
         with torch.no_grad(), self._autocast():
             # the critic's passes for GAE: on the library's GEMM with mfma_update, under the update's bf16 autocast with amp_bf16 (round 6: they ran
             # in fp32 whatever the update's precision was: 0.8 TFLOP at the fp32 rate, 8 ms of a 116 ms update), fp32 otherwise (the reference)
-            vf = self.fused_value if getattr(self, "fused_value", None) is not None else self.value_net
+            vf = self.fused_value if self.fused_value is not None else self.value_net
             # fused_norm: the critic's bf16 operand of the states, cast once here for GAE's pass and every critic pass of the update (they re-cast the same tensor otherwise)
             critic_states = self.fused_value.operand(states) if c.fused_norm else states
             values = self._f32(vf(critic_states)).reshape(T, N)
@@ -393,9 +388,8 @@ class AgentPPO:
                 info["surr_loss"] = self._policy_step(s_i, a_i, adv_i, flp_i)
             steps = c.opt_num_epochs
         info["opt_steps"] = torch.tensor(steps)                # (a tensor like every other value of info; on the host: it was counted there)
-        stats = getattr(getattr(self, "surrogate", None), "last_stats", None)
-        if stats is not None:
-            info["clip_frac"], info["approx_kl"] = stats[1], stats[2]   # of the last iteration, from the head's launch
+        if self.surrogate is not None and self.surrogate.last_stats is not None:
+            info["clip_frac"], info["approx_kl"] = self.surrogate.last_stats[1:3]   # of the last iteration, from the head's launch
         if c.fused_optimizer:
             info["grad_norm"] = self.optimizer_policy.last_grad_norm   # the policy's gradient norm before clipping, of the last iteration
         if self.fast_policy is not None:

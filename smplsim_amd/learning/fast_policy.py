@@ -16,10 +16,7 @@ import torch
 from .. import _cabi
 from .._lib import lib
 from ..batch import _check, _launch_stream, _ptr
-
-
-def _pad_to(n, m):
-    return (n + m - 1) // m * m
+from .fused_train import _pad
 
 
 class FusedPolicyInference:
@@ -38,7 +35,7 @@ class FusedPolicyInference:
         self.layers = list(policy.net.affine_layers) + [policy.action_mean]
         self.state_dim = self.layers[0].in_features
         self.action_dim = self.layers[-1].out_features
-        self.kpad = [_pad_to(l.in_features, 32) for l in self.layers]
+        self.kpad = [_pad(l.in_features, 32) for l in self.layers]
         self.w, self.b = [], []
         self._bufs = {}
         self.refresh()

@@ -10,12 +10,13 @@ fp64 sums, no atomics: the header states the order) and do not depend on how tor
     loss = value_mse(pred, target)
 
 No CPU path: the package has none.  One stream per caller: a PPOSurrogate / ValueMSE object (the module-level `ppo_surrogate` and `value_mse` are such objects)
-keeps one workspace per shape, so two calls of one object with the same shape must not be in flight on different streams; use an object per stream.
+keeps one workspace (learning/_scratch.py), so two calls of one object must not be in flight on different streams; use an object per stream.
 """
 import torch
 
 from .._lib import lib
 from ..batch import _check, _launch_stream, _ptr
+from ._scratch import Scratch
 
 
 def _rows(t, M, what):
@@ -31,22 +32,6 @@ def _matrix(t):
     if t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
         t = t.float().contiguous()
     return t, t.stride(0)
-
-
-class _Workspaces:
-    """The heads' partial-sum workspaces, one per (device, shape), kept between calls (they are overwritten before they are read, and calls on one stream
-    run in order)."""
-
-    def __init__(self):
-        self.t = {}
-
-    def get(self, device, nbytes, *shape):
-        k = (device, *shape)
-        t = self.t.get(k)
-        if t is None:
-            assert nbytes > 0, lib().ss_last_error().decode()
-            t = self.t[k] = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
-        return t
 
 
 class _Surrogate(torch.autograd.Function):
@@ -66,7 +51,7 @@ class _Surrogate(torch.autograd.Function):
         dmean = torch.empty(M, dim, dtype=torch.float32, device=dev)
         dls = torch.empty(dim, dtype=torch.float32, device=dev)
         stats = torch.empty(4, dtype=torch.float32, device=dev)
-        ws = owner.ws.get(dev, L.ss_ppo_policy_head_workspace(M, dim), M, dim)
+        ws = owner.ws.get(dev, L.ss_ppo_policy_head_workspace(M, dim))
         _check(L.ss_ppo_policy_head(_ptr(m), ldm, _ptr(a), lda, _ptr(ls), _ptr(_rows(adv, M, "adv")), _ptr(_rows(old_logp, M, "old_logp")), M, dim, float(clip_eps),
                                     None, _ptr(dmean), dim, 0, _ptr(dls), _ptr(stats), _ptr(ws), ws.numel() * 8, _launch_stream(dev)))
         owner.last_stats = stats
@@ -91,7 +76,7 @@ class _ValueMSE(torch.autograd.Function):
         L = lib()
         dpred = torch.empty(M, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        ws = owner.ws.get(dev, L.ss_value_head_workspace(M), M)
+        ws = owner.ws.get(dev, L.ss_value_head_workspace(M))
         _check(L.ss_value_head(_ptr(p), _ptr(t), M, _ptr(dpred), 1, 0, _ptr(loss), _ptr(ws), ws.numel() * 8, _launch_stream(dev)))
         ctx.save_for_backward(dpred)
         ctx.shape = pred.shape
@@ -114,7 +99,7 @@ class PPOSurrogate:
     [M, dim] and `log_std` ([dim] or [1, dim]).  Calls of one object go on one stream (its workspace is shared between them).  `last_stats`: the [loss, clip_frac, approx_kl, mean_ratio] tensor of the latest call (on the device)."""
 
     def __init__(self):
-        self.ws = _Workspaces()
+        self.ws = Scratch()
         self.last_stats = None
 
     def __call__(self, mean, log_std, actions, adv, old_logp, clip_eps):
@@ -127,7 +112,7 @@ class ValueMSE:
     between them)."""
 
     def __init__(self):
-        self.ws = _Workspaces()
+        self.ws = Scratch()
 
     def __call__(self, pred, target):
         _need_gpu("value_mse", pred, target)

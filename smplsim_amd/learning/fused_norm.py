@@ -15,6 +15,7 @@ import torch
 
 from .._lib import lib
 from ..batch import _check, _launch_stream, _ptr
+from ._scratch import Scratch
 from .fused_train import Bf16Operand, _pad
 
 _FLT_MAX = 3.4028234663852886e38
@@ -30,8 +31,8 @@ class LibRunningNorm:
         self.module = norm_module
         self.dim = int(norm_module.dim)
         self._check_buffers()
-        self._ws = {}                                               # (M, dim) -> workspace
-        self._out = {}                                              # (M, dim) -> the persistent operand tensor
+        self._ws = Scratch()
+        self._out = None                                            # the operand of the most recent M: a Bf16Operand
 
     def _check_buffers(self):
         m = self.module
@@ -53,12 +54,7 @@ class LibRunningNorm:
         self._check_buffers()
         x = self._input(x)
         m, M, L = self.module, x.shape[0], lib()
-        ws = self._ws.get((M, self.dim))
-        if ws is None:
-            need = L.ss_running_norm_workspace(M, self.dim)
-            if need < 0:
-                raise RuntimeError(L.ss_last_error().decode())
-            ws = self._ws[(M, self.dim)] = torch.empty(need // 8, dtype=torch.float64, device=x.device)
+        ws = self._ws.get(x.device, L.ss_running_norm_workspace(M, self.dim))
         _check(L.ss_running_norm_update(_ptr(x), M, self.dim, x.stride(0), _ptr(m.mean), _ptr(m.var), _ptr(m.std), _ptr(m.n), _ptr(ws), ws.numel() * 8,
                                         _launch_stream(x.device)))
         for t in (m.mean, m.var, m.std, m.n):
@@ -67,17 +63,15 @@ class LibRunningNorm:
     @torch.no_grad()
     def operand(self, x):
         """clamp((x - mean) / (std + 1e-8), -clip, clip) (x itself while n == 0), rounded to bf16 into a persistent [pad(M, 128), pad(dim, 128)] tensor whose pad rows
-        and columns are zero.  The same tensor is returned by every call with this shape: it must not be needed any more when the next call is enqueued."""
+        and columns are zero.  Consecutive calls with one M return the same tensor (only the latest M's is kept): it must not be needed any more when the next call is enqueued."""
         self._check_buffers()
         x = self._input(x)
-        m, M = self.module, x.shape[0]
-        kpad = _pad(self.dim, 128)
-        out = self._out.get((M, self.dim))
-        if out is None:
-            out = self._out[(M, self.dim)] = torch.zeros(_pad(M, 128), kpad, dtype=torch.bfloat16, device=x.device)
+        m, M, kpad = self.module, x.shape[0], _pad(self.dim, 128)
+        if self._out is None or self._out.M != M:
+            self._out = Bf16Operand(torch.zeros(_pad(M, 128), kpad, dtype=torch.bfloat16, device=x.device), M, self.dim)
         _check(lib().ss_obs_to_bf16(_ptr(x), M, self.dim, x.stride(0), _ptr(m.mean), _ptr(m.std), _ptr(m.n), -_FLT_MAX, _FLT_MAX,
-                                    float(m.clip) if m.clip else _FLT_MAX, _ptr(out), kpad, _launch_stream(x.device)))
-        return Bf16Operand(out, M, self.dim)
+                                    float(m.clip) if m.clip else _FLT_MAX, _ptr(self._out.t), kpad, _launch_stream(x.device)))
+        return self._out
 
     def __call__(self, x):
         if self.module.training:

@@ -19,6 +19,7 @@ import torch
 from .. import _cabi
 from .._lib import lib
 from ..batch import _check, _launch_stream
+from ._scratch import Scratch
 
 _REFUSED = ("amsgrad", "maximize", "capturable", "differentiable", "decoupled_weight_decay")
 
@@ -45,7 +46,7 @@ class LibAdam(torch.optim.Adam):
         self.max_grad_norm = max_grad_norm
         self.last_grad_norm = None
         self._images = {}                                           # id(param) -> (w_bf16, wt_bf16)
-        self._ws = {}                                               # tiles -> workspace
+        self._ws = Scratch()
         self._norm = None
 
     # ------------------------------------------------------------------ images
@@ -156,13 +157,8 @@ class LibAdam(torch.optim.Adam):
                     keep.append(g)
                     if id(p) not in self._images:
                         torch.autograd.graph.increment_version(p)   # written in place behind torch's back: say so (parameters with images: see attach_images)
-                need = L.ss_adam_step_workspace(table, len(chunk))
-                if need < 0:
-                    raise RuntimeError(L.ss_last_error().decode())
-                ws = self._ws.get((dev, need))
-                if ws is None:
-                    ws = self._ws[(dev, need)] = torch.empty(need // 8, dtype=torch.float64, device=dev)
+                ws = self._ws.get(dev, L.ss_adam_step_workspace(table, len(chunk)))
                 _check(L.ss_adam_step(table, len(chunk), step, lr, b1, b2, eps, wd, float(clip) if clip is not None else 0.0, ctypes.c_void_p(self._norm.data_ptr()),
-                                      ctypes.c_void_p(ws.data_ptr()), need, _launch_stream(dev)))
+                                      ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, _launch_stream(dev)))
             self.last_grad_norm = self._norm[0]
         return loss

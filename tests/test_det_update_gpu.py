@@ -271,6 +271,30 @@ def test_fused_mlp_train_deterministic_is_reproducible_and_close_to_the_default(
         assert r < FUSED_REL, (i, tuple(params[i].shape), r)
 
 
+def test_fused_mlp_train_gradients_of_a_shorter_batch_do_not_take_in_the_longer_ones_rows():
+    """One FusedMLPTrain(deterministic=True) object at (512, 256, 256), heads of 69 and of 1: gradients at 1000 rows, then on x[:900] — the same 1024 padded rows, and
+    every weight gradient contracts over all of them.  The second pass's gradients are bit-identical to those of a fresh object that only ever saw x[:900]: the
+    work tensors of a pass belong to its exact row count, so rows 900..999 of the first pass's operand and dZ reach nothing."""
+    from smplsim_amd.learning.fused_train import FusedMLPTrain
+    from smplsim_amd.learning.networks import MLP
+    for out_dim in (69, 1):
+        torch.manual_seed(out_dim)
+        net = MLP(289, (512, 256, 256), "silu").cuda()
+        head = torch.nn.Linear(256, out_dim).cuda()
+        params = [p for l in list(net.affine_layers) + [head] for p in (l.weight, l.bias)]
+        x = torch.randn(1000, 289, device="cuda") * 2
+        target = torch.randn(1000, out_dim, device="cuda")
+
+        def grads(fused, M):
+            return [g.clone() for g in torch.autograd.grad((fused(x[:M]) * target[:M]).sum(), params)]
+
+        used = FusedMLPTrain(net.affine_layers, head, "silu", deterministic=True)
+        grads(used, 1000)
+        got, want = grads(used, 900), grads(FusedMLPTrain(net.affine_layers, head, "silu", deterministic=True), 900)
+        for i, (a, b) in enumerate(zip(got, want)):
+            assert torch.equal(_bits(a), _bits(b)), (out_dim, i, tuple(a.shape), float((a - b).abs().max()))
+
+
 # ---------------------------------------------------------------------------------------------------------------- 5: end to end
 def _agent_state(agent):
     out = {}

@@ -150,21 +150,86 @@ def test_fused_train_has_no_cpu_path():
 
 
 def test_fused_train_work_tensors_are_reused_only_between_finished_passes():
-    """learning.fused_train._Buffers (host logic, no kernel): a pass's work tensors are kept between calls, initialised once (the ones row behind a
-    transposed activation), keyed by shape; a pass that starts while the previous one's backward has not run gets fresh tensors."""
-    from smplsim_amd.learning.fused_train import _Buffers
-    b = _Buffers()
+    """learning.fused_train._WorkSets (host logic, no kernel): a pass's work tensors are kept between finished passes, initialised once (the ones column of the
+    head's bias gradient), one set per exact row count; a pass that starts while the set's holder is alive gets fresh tensors; a set never carries rows of a longer
+    batch; an abandoned holder or an exception holds nothing; at most three sets are kept, least recently used first out."""
+    import gc
+    from smplsim_amd.learning.fused_train import _WorkSets
+
+    class Ctx:                                                 # stands in for the autograd ctx of a tracked pass
+        pass
+    w = _WorkSets("cpu", lambda Mp: (None, 0))                 # (no layer plan: nothing here depends on one)
     calls = []
 
     def init(t):
         calls.append(1)
         t[2, :3] = 1.0
-    t1 = b.get("ht", (4, 8), torch.float32, "cpu", False, init)
+
+    def tensors(ws, cols=8):
+        return ws.get("ht", (ws.Mp, cols), torch.float32, init)
+    ctx = Ctx()
+    s1 = w.take(200, ctx)
+    assert (s1.M, s1.Mp) == (200, 256)
+    t1 = tensors(s1)
     t1[0, 0] = 5.0
-    t2 = b.get("ht", (4, 8), torch.float32, "cpu", False, init)
-    assert t2 is t1 and len(calls) == 1 and float(t2[2, :3].sum()) == 3.0 and float(t2[0, 0]) == 5.0     # kept, initialised once
-    t3 = b.get("ht", (4, 16), torch.float32, "cpu", False, init)
-    assert t3 is not t1 and tuple(t3.shape) == (4, 16) and len(calls) == 2                                 # another shape: another tensor
-    f = b.get("ht", (4, 8), torch.float32, "cpu", True, init)
-    assert f is not t1 and float(f[0, 0]) == 0.0 and float(f[2, :3].sum()) == 3.0 and len(calls) == 3       # fresh: zeroed and initialised
-    assert b.busy is False
+    s1.held = None                                             # what the end of backward does
+    s2 = w.take(200)                                           # a no-grad pass: holds nothing after it returns
+    t2 = tensors(s2)
+    assert s2 is s1 and t2 is t1 and len(calls) == 1 and float(t2[2, :3].sum()) == 3.0 and float(t2[0, 0]) == 5.0     # kept, initialised once
+    t3 = s2.get("ht16", (s2.Mp, 16), torch.float32, init)
+    assert t3 is not t1 and tuple(t3.shape) == (256, 16) and len(calls) == 2                               # another request: another tensor
+    ctx = Ctx()
+    assert w.take(200, ctx) is s1
+    for holder in (Ctx(), None):                               # a tracked and a no-grad pass while ctx is alive
+        f = w.take(200, holder)
+        ft = tensors(f)
+        assert f is not s1 and ft is not t1 and float(ft[0, 0]) == 0.0 and float(ft[2, :3].sum()) == 3.0   # fresh: zeroed and initialised
+    assert len(calls) == 4 and s1.held() is ctx                # ... and ctx's set is still ctx's: the newest set is kept in its place
+    cur = w.take(200)
+    assert cur is f and w.take(200) is cur
+    # a smaller M with the same padded rows never sees the longer batch's rows
+    tensors(cur)[150, :] = 7.0
+    s130 = w.take(130)
+    assert s130 is not cur and s130.Mp == cur.Mp == 256 and float(tensors(s130)[150].abs().sum()) == 0.0
+    # a holder dropped without a backward: the next pass at that M gets the kept tensors back
+    ctx = Ctx()
+    assert w.take(200, ctx) is cur and cur.held() is ctx
+    ptr = tensors(cur).data_ptr()
+    del ctx
+    gc.collect()
+    assert cur.held() is None and tensors(w.take(200)).data_ptr() == ptr and float(tensors(cur)[150, 0]) == 7.0
+    # an exception between take and release: nothing stays held
+
+    def failing_pass():
+        ctx = Ctx()
+        ctx.work = w.take(200, ctx)
+        raise ValueError("a kernel refused its arguments")
+    with pytest.raises(ValueError):
+        failing_pass()
+    gc.collect()
+    assert cur.held() is None and tensors(w.take(200)).data_ptr() == ptr
+    # four row counts: the least recently used set goes, the other three stay what they were
+    kept = {M: w.take(M) for M in (130, 200, 300)}
+    assert kept[200] is cur and kept[130] is s130 and sorted(w.sets) == [130, 200, 300]
+    tensors(kept[130])[1, 1] = 9.0
+    kept[400] = w.take(400)
+    assert sorted(w.sets) == [200, 300, 400] and all(w.take(M) is kept[M] for M in (200, 300, 400))
+    again = w.take(130)
+    assert again is not kept[130] and float(tensors(again)[1, 1]) == 0.0 and float(tensors(again)[2, :3].sum()) == 3.0
+
+
+def test_scratch_raises_the_librarys_message_for_a_refused_workspace_query():
+    """learning._scratch.Scratch: one grow-only workspace per device; a negative `_workspace` answer becomes a RuntimeError that carries ss_last_error()."""
+    from smplsim_amd._lib import lib
+    from smplsim_amd.learning._scratch import Scratch
+    L, sc = lib(), Scratch()
+    need = L.ss_wgrad_bf16_det_workspace(1024, 64, 64)
+    a = sc.get("cpu", need)
+    assert a.dtype == torch.float64 and a.numel() * 8 >= need > 0 and sc.get("cpu", need - 8) is a          # a smaller request: the same buffer
+    b = sc.get("cpu", need + 8)
+    assert b is not a and b.numel() * 8 >= need + 8 and sc.get("cpu", need) is b                             # grown once, never shrunk
+    bad = L.ss_wgrad_bf16_det_workspace(0, 64, 64)
+    assert bad < 0
+    with pytest.raises(RuntimeError, match="ss_wgrad_bf16_det_workspace"):
+        sc.get("cpu", bad)
+    assert sc.get("cpu", need) is b
