@@ -239,6 +239,40 @@ typedef struct ss_gather_tensor {
 } ss_gather_tensor;
 int ss_gather_rows(const ss_gather_tensor *tensors, int32_t count, const int64_t *perm, int32_t src_rows, int32_t rows, int32_t block_rows, void *stream);
 
+/* ss_episode_stats: the episode statistics of a rollout — what the reference's sampler collects step by step in a LoggerRL (smpl_sim/learning/logger_rl.py:
+ * start_episode / step / end_episode, agents/agent.py:64-109) and its training line is made of (agent_humanoid.py:171-193).  N envs advance in lock step for T
+ * steps, so an episode spans many rollouts: the return and the length of the episode every env is in the middle of are a per-env carry, read and rewritten.
+ *   rewards, not_done   [T, N] f32, time-major, dense: the rollout tensors that ss_gae reads.
+ *   parts               [T, N, P] f32, dense: the reward terms of every step; NULL when P == 0.  0 <= P <= SS_EPISODE_MAX_PARTS.
+ *   ep_return [N] f64, ep_len [N] int32   the carry (a new env: 0, 0).
+ *   stats [9 + P] f64   overwritten, in the order of the SS_EP_* indices; nothing behind element 9 + P - 1 is touched.
+ * Per env column n, with t ascending from 0:  ep_return[n] += (double)rewards[t, n];  ep_len[n] += 1;  where not_done[t, n] == 0.0f (+0 or -0; any other value, a
+ * NaN included, continues the episode) the episode ends: num_episodes += 1, total_episode_reward += ep_return[n], total_episode_len += ep_len[n], the episode
+ * minimum and maximum take ep_return[n], and both carries go to zero.  Over all steps: num_steps = T * N, total_reward and the minimum and maximum reward, and
+ * stats[9 + p] = the sum of parts[:, :, p].  With no episode ended min_episode_reward = +inf and max_episode_reward = -inf (LoggerRL's initial values).
+ * Minima and maxima propagate a NaN (torch.amin / amax); a NaN reward makes the sums it enters NaN and its env's ep_return NaN until that episode ends; it changes
+ * no other env's carry and no count.  ep_len wraps after 2^31 - 1 steps of one episode; counts and lengths are summed as integers held in fp64 (exact below 2^53).
+ * Reproducible like the loss heads, ss_adam_step and ss_running_norm_update: no atomics, every output a function of the arguments and the input bytes alone — not
+ * of the order in which workgroups run, nor of what the workspace held before.  Two launches on `stream` (scan, reduce), no host synchronisation, nothing read
+ * back; the workspace is caller-owned, 16-byte aligned, and may be reused by the next call on the same stream.
+ *   workspace  at least ss_episode_stats_workspace(T, N, P) = ceil(N / 64) * (9 + P) * 8 bytes.  After the call it holds G = ceil(N / 64) rows of 9 + P doubles, dense,
+ *              in the layout of stats: row g is the statistics of the columns [64 g, min(64 g + 64, N)).
+ *   order      an episode's return: the fp64 sum of its fp32 rewards with t ascending, continued from the carry (fixed by the definition: ep_return, ep_len, the
+ *              counts and the four extremes are the same in any implementation).  The sums: workgroup g is ONE wavefront and owns the columns 64 g .. 64 g + 63, one
+ *              per lane, so that every [t, :] row access is a coalesced segment; lane l adds what column 64 g + l contributes with t ascending (an episode's return
+ *              and length at the step that ends it; with P == 4 and a 16-byte aligned parts a step's four terms come by one 16-byte load), a lane beyond N adds
+ *              nothing; the 64 lanes meet by the xor butterfly (distances 32, 16, 8, 4, 2, 1) and lane 0 stores row g; the reduce, one wavefront with lane j on
+ *              statistic j, folds (((row_0 + row_1) + row_2) + ... + row_{G-1}), ascending from row 0.  One wavefront per workgroup because the scan has only N
+ *              columns to hand out: 4096 columns are 64 workgroups on 64 CUs rather than 16 of 256 lanes, without LDS or a barrier.  Not timed.
+ * SS_ERR_INVALID, nothing launched: a null required pointer; parts null with P > 0; T < 1, N < 1 or P outside [0, 8]; a null, misaligned or too-small workspace.
+ * The query returns a negative value (and sets ss_last_error) for invalid shapes. */
+#define SS_EPISODE_MAX_PARTS 8
+enum { SS_EP_NUM_STEPS, SS_EP_NUM_EPISODES, SS_EP_TOTAL_EPISODE_REWARD, SS_EP_TOTAL_EPISODE_LEN, SS_EP_MIN_EPISODE_REWARD,
+       SS_EP_MAX_EPISODE_REWARD, SS_EP_TOTAL_REWARD, SS_EP_MIN_REWARD, SS_EP_MAX_REWARD, SS_EP_PARTS /* = 9: first of P part sums */ };
+int64_t ss_episode_stats_workspace(int32_t T, int32_t N, int32_t P);
+int ss_episode_stats(const float *rewards, const float *not_done, const float *parts, int32_t T, int32_t N, int32_t P,
+                     double *ep_return, int32_t *ep_len, double *stats, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Test hook: the GEMM instantiation launched last by an ss_linear_* / ss_wgrad_bf16* call on the calling host thread, as
  * "<family> mode=<G256 mode or -> bn=<BN> bk=<BK> waves=<waves per workgroup> out=<bf16|f32|f32acc|f32det> ksplit=<K shares> kper=<K tiles per share>"
  * with family linear / glds / train / gemm256 / wgrad (empty before the first launch).  The deterministic entries report their GEMM, not their reduce pass:

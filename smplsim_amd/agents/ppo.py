@@ -53,6 +53,7 @@ class PPOConfig:
     fused_norm: bool = False       # with mfma_update: the policy's train-mode RunningNorm by the library's kernels (learning/fused_norm.py) and the networks' bf16 inputs made once, not once per pass
     use_mini_batch: bool = False   # update: mini-batch epochs (agent_ppo.py:26-46): per epoch a permutation of the batch and floor(M / mini_batch_size) iterations of one critic step + one policy step
     mini_batch_size: int = 0       # rows per mini-batch (with use_mini_batch: >= 1, and at most the rollout's rows at update time)
+    episode_stats: bool = False    # sampler: episode returns and lengths across rollouts, reward extremes and the means of the env's reward terms (learning/episode_stats.py)
     extra: dict = field(default_factory=dict)
 
 
@@ -74,7 +75,7 @@ def _check_flags(c, device):
 
 
 class AgentPPO:
-    fast_policy = fused_policy = fused_value = lib_norm = surrogate = value_mse = _shuffled = None   # the optional parts: None = off (also on an object that __init__ never saw)
+    fast_policy = fused_policy = fused_value = lib_norm = surrogate = value_mse = _shuffled = episode_stats = None   # the optional parts: None = off (also on an object that __init__ never saw)
 
     def __init__(self, env, cfg=None, seed=0):
         self.env, self.cfg = env, cfg or PPOConfig()
@@ -123,6 +124,11 @@ class AgentPPO:
         if c.fused_loss:
             from ..learning.fused_loss import PPOSurrogate, ValueMSE
             self.surrogate, self.value_mse = PPOSurrogate(), ValueMSE()
+        if c.episode_stats:
+            # the carry of the episodes in flight lives here, across rollouts; it is not part of a checkpoint (the env states are not either: after a resume
+            # episodes are counted from the resume point)
+            from ..learning.episode_stats import EpisodeStats
+            self.episode_stats = EpisodeStats(env.num_envs, self.device, getattr(env, "reward_part_names", ()))
 
     # ------------------------------------------------------------------ sampling
     def _prep_obs(self, obs):
@@ -160,20 +166,24 @@ class AgentPPO:
             a = mean if mean_action else mean + self.policy_net.action_log_std.exp() * noise
             act_row.copy_(a)
             a_env = self._prep_actions(a)
-        obs, rew, died, timed_out, _ = step_fn(a_env)
+        obs, rew, died, timed_out, info = step_fn(a_env)
         buf["rewards"][t, r] = rew
+        if buf["parts"] is not None:
+            buf["parts"][t, r] = info["reward_parts"]           # (episode_stats; the env reuses one buffer: copied this step)
         buf["dead"][t, r] = died                               # (boolean rows: one launch each; turned into the float masks once, in _rollout_out)
         torch.logical_or(died, timed_out, out=buf["done"][t, r])
         return obs
 
     def _rollout_buffers(self, T, N, mean_action):
         f = dict(device=self.device, dtype=torch.float32)
+        parts = len(self.episode_stats.part_names) if self.episode_stats is not None else 0
         # bf16 sampler: the behaviour policy's own log-densities go into the batch (the update's fp32 network would give the PPO
         # ratio a denominator from a slightly different policy: a mean error of 1e-2 at sigma 0.08 moves log-probs noticeably)
         return dict(states=torch.empty(T, N, self.state_dim, **f), actions=torch.empty(T, N, self.action_dim, **f),
                     rewards=torch.empty(T, N, **f), dead=torch.empty(T, N, dtype=torch.bool, device=self.device),
                     done=torch.empty(T, N, dtype=torch.bool, device=self.device), a_env=torch.empty(N, self.action_dim, **f),
-                    logp=torch.empty(T, N, 1, **f) if (self.fast_policy is not None and not mean_action) else None)
+                    logp=torch.empty(T, N, 1, **f) if (self.fast_policy is not None and not mean_action) else None,
+                    parts=torch.empty(T, N, parts, **f) if parts else None)
 
     def _rollout_out(self, buf, last_obs_rows, mean_action):
         T, N = buf["rewards"].shape
@@ -186,6 +196,11 @@ class AgentPPO:
                    not_dead=(~buf["dead"]).to(torch.float32), exps=torch.full((T, N), 0.0 if mean_action else 1.0, **f), last_state=last)
         if buf["logp"] is not None:
             out["log_probs"] = buf["logp"]
+        if self.episode_stats is not None:
+            # two launches per rollout, mean-action rollouts included (their episodes are episodes); [9 + P] float64 on the device, read by update_params' info
+            out["episode_stats"] = self.episode_stats.update(out["rewards"], out["not_done"], buf["parts"])
+            if buf["parts"] is not None:
+                out["reward_parts"] = buf["parts"]
         return out
 
     @torch.no_grad()
@@ -397,6 +412,8 @@ class AgentPPO:
         self.epoch += 1
         info["mean_reward"] = batch["rewards"].mean()
         info["episodes_ended"] = (1.0 - batch["not_done"]).sum()
+        if self.episode_stats is not None and "episode_stats" in batch:
+            info.update(self.episode_stats.as_tensors(batch["episode_stats"]))   # the reference's names (LoggerRL), 0-dim tensors like every other value
         return info
 
     def optimize_policy(self, epochs=1):

@@ -1,6 +1,6 @@
 // smplsim_mlp.hip — host side of the policy MLP and the PPO update on gfx950: the launch planning of the bf16 GEMMs and the C ABI
 // (include/smplsim_mlp.h) of every learning entry point.  The kernels are in headers: ss_gemm128.h (128-row tiles, shared pieces),
-// ss_gemm256.h / ss_gemm256_kernels.h (256 x 256 tiles, weight gradient), ss_sampler.h, ss_ppo_head.h, ss_optim.h, ss_norm.h, ss_gather.h.
+// ss_gemm256.h / ss_gemm256_kernels.h (256 x 256 tiles, weight gradient), ss_sampler.h, ss_ppo_head.h, ss_optim.h, ss_norm.h, ss_gather.h, ss_episode.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +17,7 @@
 #include "ss_optim.h"
 #include "ss_norm.h"
 #include "ss_gather.h"
+#include "ss_episode.h"
 
 namespace {
 
@@ -457,6 +458,32 @@ int ss_running_norm_update(const float *x, int32_t M, int32_t dim, int32_t ldx, 
   hipLaunchKernelGGL(run_norm::ss_norm_partials_kernel, dim3((unsigned)(P * groups)), dim3(256), 0, st, x, M, dim, ldx, (int)groups, part);
   hipLaunchKernelGGL(run_norm::ss_norm_merge_kernel, dim3(1), dim3(256), 0, st, static_cast<const double *>(part), (int)P, M, dim, mean, var, sd,
                      reinterpret_cast<long long *>(n));
+  return launched();
+}
+
+// ---- episode statistics of a rollout (ss_episode.h): two launches on `stream`, one partial row per 64 env columns into the caller's workspace, then the fixed-order fold
+static int64_t episode_stats_bytes(int32_t N, int32_t P) { return row_groups(N, episode::LANES) * (episode::NFIXED + P) * 8; }
+
+int64_t ss_episode_stats_workspace(int32_t T, int32_t N, int32_t P) {
+  if (T < 1 || N < 1 || P < 0 || P > SS_EPISODE_MAX_PARTS) {
+    fail(SS_ERR_INVALID, "ss_episode_stats_workspace: T >= 1, N >= 1, 0 <= P <= 8");
+    return -1;
+  }
+  return episode_stats_bytes(N, P);
+}
+
+int ss_episode_stats(const float *rewards, const float *not_done, const float *parts, int32_t T, int32_t N, int32_t P, double *ep_return, int32_t *ep_len,
+                     double *stats, void *workspace, int64_t workspace_bytes, void *stream) {
+  if (!rewards || !not_done || !ep_return || !ep_len || !stats) return fail(SS_ERR_INVALID, "null argument");
+  if (T < 1 || N < 1 || P < 0 || P > SS_EPISODE_MAX_PARTS) return fail(SS_ERR_INVALID, "ss_episode_stats: T >= 1, N >= 1, 0 <= P <= 8");
+  if (P > 0 && !parts) return fail(SS_ERR_INVALID, "ss_episode_stats: parts is null with P > 0");
+  if (check_workspace(workspace, workspace_bytes, episode_stats_bytes(N, P)) != SS_OK) return SS_ERR_INVALID;
+  const int G = (int)row_groups(N, episode::LANES), W = episode::NFIXED + P;
+  const episode::ScanArgs a{rewards, not_done, P > 0 ? parts : nullptr, ep_return, ep_len, static_cast<double *>(workspace), T, N, P};
+  hipStream_t st = (hipStream_t)stream;
+  if (P == 4 && !(reinterpret_cast<size_t>(parts) & 15)) hipLaunchKernelGGL(episode::ss_episode_scan_kernel<true>, dim3((unsigned)G), dim3(episode::LANES), 0, st, a);
+  else hipLaunchKernelGGL(episode::ss_episode_scan_kernel<false>, dim3((unsigned)G), dim3(episode::LANES), 0, st, a);
+  hipLaunchKernelGGL(episode::ss_episode_reduce_kernel, dim3(1), dim3(episode::LANES), 0, st, static_cast<const double *>(a.part), G, W, (double)T * (double)N, stats);
   return launched();
 }
 

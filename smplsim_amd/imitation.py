@@ -25,6 +25,8 @@ from ._lib import lib
 
 
 class SMPLSimImitationVecEnv:
+    reward_part_names = ("pos", "rot", "vel", "ang_vel")        # the columns of info["reward_parts"] (ss_imitation_step: the four exp(-k e) terms of the reward, before their weights)
+
     def __init__(self, num_envs, motion_lib, model=None, device=0, self_obs_v=2, control_freq_inv=15, sim_timestep_inv=450,
                  termination_distance=0.25, reward_k=(100.0, 10.0, 0.1, 0.1), reward_w=(0.5, 0.3, 0.1, 0.1),
                  random_start=True, autoreset=True, seed=0, fused=True, **env_kw):

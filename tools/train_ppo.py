@@ -9,6 +9,7 @@
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -36,6 +37,7 @@ def main():
     ap.add_argument("--fused-optimizer", action="store_true", help="update: gradient clipping and Adam by the library's optimiser step (learning/fused_optim.py; adds grad_norm to the log line)")
     ap.add_argument("--fused-norm", action="store_true", help="with --mfma-update: the policy's train-mode RunningNorm by the library's kernels and the networks' bf16 inputs made once (learning/fused_norm.py)")
     ap.add_argument("--mini-batch-size", type=int, default=0, help="update: mini-batch epochs of this many rows, the batch shuffled on the device once per epoch (0 = full-batch epochs; adds opt_steps to the log line)")
+    ap.add_argument("--episode-stats", action="store_true", help="sampler: episode returns and lengths across rollouts and the means of the reward terms (learning/episode_stats.py; adds avg_episode_reward, avg_episode_len, ... to the log line, non-finite values left out)")
     ap.add_argument("--save", default="")
     ap.add_argument("--log-every", type=int, default=1)
     ap.add_argument("--motion-file", default="", help="HumanoidIm: AMASS-style pickle ({key: {pose_aa, trans, fps}}); default = synthetic clips")
@@ -58,7 +60,7 @@ def main():
         env = SMPLSimVecEnv(args.envs, task=args.task, autoreset=True, seed=0)
     cfg = PPOConfig(hidden=tuple(int(x) for x in args.hidden.split(",")), min_batch_size=args.min_batch_size, opt_num_epochs=args.opt_epochs, amp_bf16=args.amp_bf16, mfma_inference=args.mfma_inference, mfma_update=args.mfma_update,
                     deterministic_update=args.deterministic_update, fused_loss=args.fused_loss, fused_optimizer=args.fused_optimizer, fused_norm=args.fused_norm,
-                    use_mini_batch=args.mini_batch_size > 0, mini_batch_size=args.mini_batch_size)
+                    use_mini_batch=args.mini_batch_size > 0, mini_batch_size=args.mini_batch_size, episode_stats=args.episode_stats)
     agent = AgentPPO(env, cfg, seed=0)
     ts, tu, n = 0.0, 0.0, 0
     for ep in range(args.epochs):
@@ -73,6 +75,9 @@ def main():
         if ep % args.log_every and ep != args.epochs - 1:
             continue
         ep_len = float(T * N / max(1.0, float((1.0 - batch["not_done"]).sum())))
+        if args.episode_stats:                               # no episode ended in the rollout: its averages are NaN and its extremes infinite: left out of the line
+            named = agent.episode_stats.as_dict(batch["episode_stats"])
+            info = {k: v for k, v in info.items() if k not in named or math.isfinite(named[k])}
         print(json.dumps({"epoch": ep, "samples": T * N, "sample_s": round(t1 - t0, 4), "update_s": round(t2 - t1, 4),
                           "mean_episode_len": round(ep_len, 1),
                           **{k: round(float(v), 5) for k, v in info.items()}}))
