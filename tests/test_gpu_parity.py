@@ -1225,7 +1225,8 @@ def test_linear_bf16_dx_result_and_column_sums():
 def test_fused_mlp_train_gradients_match_autograd():
     """learning.fused_train.FusedMLPTrain (forward + backward on ss_linear_bf16_train) against torch autograd over the same layers in
     fp32: outputs and every parameter gradient agree to bf16 round-off through the stack (relative to the gradient's own scale), on the
-    PPO losses' shapes: the policy's 69-wide head and the value's 1-wide head, a batch that is not a multiple of 64."""
+    PPO losses' shapes: the policy's 69-wide head and the value's 1-wide head, a batch that is not a multiple of 64.
+    (The tight comparison, against a float64 pass that rounds where the kernels round, is tests/test_fused_mlp_gpu.py.)"""
     from smplsim_amd.learning.fused_train import FusedMLPTrain
     from smplsim_amd.learning.networks import MLP
     torch.manual_seed(0)
