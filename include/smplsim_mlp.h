@@ -273,6 +273,47 @@ int64_t ss_episode_stats_workspace(int32_t T, int32_t N, int32_t P);
 int ss_episode_stats(const float *rewards, const float *not_done, const float *parts, int32_t T, int32_t N, int32_t P,
                      double *ep_return, int32_t *ep_len, double *stats, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ss_clip_outcomes: which clip every env of a motion-imitation rollout was tracking when it fell, when it finished and while it stepped, tallied into per-clip
+ * counters — the input of the reference's failure-weighted sampling (smpl_sim/smpllib/motion_lib_base.py:219-267: termination_history,
+ * update_soft_sampling_weight), which collects it on the host from the keys of the failed clips.
+ *   clip_ids     [T, N] int32, time-major, dense: the clip env n was tracking DURING step t (the env's motion_ids before the step launch: the fused step
+ *                overwrites them when it re-initialises a finished env).
+ *   dead, done   [T, N] bytes, dense: the sampler's rows (torch.bool storage); any non-zero byte is set.
+ *   counts       [M, 3] int64, dense, ACCUMULATED: the call adds to what it finds and never zeroes.  Columns: SS_CLIP_FAILED, SS_CLIP_COMPLETED, SS_CLIP_STEPS.
+ * Per element (t, n) with c = clip_ids[t, n]:  counts[c, SS_CLIP_STEPS] += 1;  if dead[t, n] != 0, counts[c, SS_CLIP_FAILED] += 1;  otherwise, if done[t, n] != 0,
+ * counts[c, SS_CLIP_COMPLETED] += 1.  A c outside [0, M) skips the element entirely: nothing is added anywhere for it, and the kernel compares c with the range
+ * before it forms an address from it (as ss_gather_rows does with perm).  Nothing but the 3 M counters is written.  Sums wrap modulo 2^64.
+ * Reproducible although it uses atomics: the additions are 64-bit INTEGER vector atomics (no return value), and integer addition is exact and independent of
+ * order, so the counters are a function of the arguments and the input bytes alone — not of the order in which workgroups run.  No float is summed anywhere.
+ *   order      irrelevant to the result; for the cost: workgroup g is ONE wavefront and owns the env columns 64 g .. 64 g + 63, one per lane (every [t, :] row
+ *              access a coalesced segment); a lane walks t ascending, counts the steps of the clip it is on in a register and adds them to the clip's counter
+ *              when the id changes, when dead or done is set, and at the end of the column: (episodes + id changes + N) adds instead of T * N (12 - 37 us for a
+ *              25 x 2048 rollout, the more the fewer clips share the adds: profiles/clip_sampling.txt).
+ * One launch on `stream`, no workspace, no host synchronisation, nothing read back.  SS_ERR_INVALID, nothing launched: a null pointer; T, N or M < 1; counts not
+ * 8-byte aligned.
+ *
+ * ss_clip_sampling_cdf: the counters' failure column as the sampling CDF that ss_motion_resample and the fused imitation step search ("the smallest m with
+ * cdf[m] > draw") — the reference's update_sampling_prob (p proportional to the termination history, uniform while nothing has failed), mixed with a uniform floor.
+ *   counts       [M, 3] int64 as above, not modified; only column SS_CLIP_FAILED is read: f_m = max(counts[m, SS_CLIP_FAILED], 0) (a negative count is 0).
+ *   uniform_mix  u in [0, 1]: the share of the uniform distribution.  u = 0 is the reference's rule; u > 0 keeps a clip that never failed in play (the floor is
+ *                the u / M term alone: SS_CLIP_COMPLETED and SS_CLIP_STEPS play no part).
+ *   cdf          [M] f32, overwritten.  Meant to be the array already bound into the fused step: the step launches behind this call on the stream draw from it.
+ *   prob         [M] f64, overwritten, or NULL.
+ * Every value is formed in fp64 and every operation is rounded on its own (no FMA: the kernel switches contraction off), in this order:
+ *   S = sum_m f_m as an integer (int64; it must stay below 2^63), then (double)S;  keep = 1 - u,  floor = u / M,  uniform = 1 / M, each once;
+ *   q_m = (double)f_m / (double)S if S > 0, else uniform;   p_m = keep * q_m + floor  (one multiplication, then one addition);
+ *   c_0 = p_0,  c_m = c_{m-1} + p_m, added SEQUENTIALLY with m ascending (the order of numpy.cumsum);
+ *   cdf[m] = (float)c_m for m < M - 1;  cdf[M - 1] = (float)(1 + 1e-6) = 1.00000095f, the sentinel MotionLibSMPL.load_motions writes: a draw below 1 always lands in
+ *   a clip;  prob[m] = p_m.
+ * With u = 0 a clip with f_m = 0 has p_m = 0 exactly, so cdf[m] == cdf[m - 1] (cdf[0] == 0) and no draw in [0, 1) selects it.  The sequential sum IS the contract:
+ * one lane runs the chain (a parallel scan would change the bits); M is at most tens of thousands and the call runs once per rollout (7 us up to 256 clips, 0.93 ms at
+ * 50 000: profiles/clip_sampling.txt).
+ * A function of the arguments and the input bytes alone.  One launch on `stream` (one workgroup), no workspace, no host synchronisation.
+ * SS_ERR_INVALID, nothing launched: a null counts or cdf; M < 1; u outside [0, 1] or NaN. */
+enum { SS_CLIP_FAILED, SS_CLIP_COMPLETED, SS_CLIP_STEPS, SS_CLIP_COLUMNS /* = 3 */ };
+int ss_clip_outcomes(const int32_t *clip_ids, const uint8_t *dead, const uint8_t *done, int32_t T, int32_t N, int32_t M, int64_t *counts, void *stream);
+int ss_clip_sampling_cdf(const int64_t *counts, int32_t M, double uniform_mix, float *cdf, double *prob, void *stream);
+
 /* Test hook: the GEMM instantiation launched last by an ss_linear_* / ss_wgrad_bf16* call on the calling host thread, as
  * "<family> mode=<G256 mode or -> bn=<BN> bk=<BK> waves=<waves per workgroup> out=<bf16|f32|f32acc|f32det> ksplit=<K shares> kper=<K tiles per share>"
  * with family linear / glds / train / gemm256 / wgrad (empty before the first launch).  The deterministic entries report their GEMM, not their reduce pass:

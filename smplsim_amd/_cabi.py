@@ -145,7 +145,8 @@ ACTIVATIONS = {"none": 0, "silu": 1, "tanh": 2, "relu": 3}
 MLP_EXPORTS = ["ss_linear_bf16", "ss_linear_bf16_train", "ss_linear_bf16_dx", "ss_wgrad_bf16", "ss_obs_to_bf16", "ss_gaussian_sample",
                "ss_debug_last_gemm", "ss_linear_bf16_dx_det", "ss_linear_bf16_dx_det_workspace", "ss_wgrad_bf16_det", "ss_wgrad_bf16_det_workspace",
                "ss_ppo_policy_head", "ss_ppo_policy_head_workspace", "ss_value_head", "ss_value_head_workspace", "ss_adam_step", "ss_adam_step_workspace",
-               "ss_running_norm_update", "ss_running_norm_workspace", "ss_gather_rows", "ss_episode_stats", "ss_episode_stats_workspace"]            # include/smplsim_mlp.h (product library only: the matrix-core kernels)
+               "ss_running_norm_update", "ss_running_norm_workspace", "ss_gather_rows", "ss_episode_stats", "ss_episode_stats_workspace",
+               "ss_clip_outcomes", "ss_clip_sampling_cdf"]            # include/smplsim_mlp.h (product library only: the matrix-core kernels)
 
 
 class AdamTensor(C.Structure):
@@ -167,6 +168,8 @@ EPISODE_MAX_PARTS = 8            # SS_EPISODE_MAX_PARTS: reward terms of one ss_
 # SS_EP_*: the fixed statistics of ss_episode_stats, in the order of `stats`; the P part sums follow
 EPISODE_STATS = ("num_steps", "num_episodes", "total_episode_reward", "total_episode_len", "min_episode_reward", "max_episode_reward", "total_reward",
                  "min_reward", "max_reward")
+# SS_CLIP_*: the columns of the [M, 3] int64 counters of ss_clip_outcomes
+CLIP_COLUMNS = ("failed", "completed", "steps")
 
 
 def bind_mlp(lib):
@@ -199,6 +202,10 @@ def bind_mlp(lib):
     # (rewards, not_done, parts, T, N, P, ep_return, ep_len, stats, workspace, bytes, stream)
     lib.ss_episode_stats.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int64, vp]
     lib.ss_episode_stats_workspace.argtypes = [C.c_int32, C.c_int32, C.c_int32]; lib.ss_episode_stats_workspace.restype = C.c_int64
+    # (clip_ids, dead, done, T, N, M, counts, stream)
+    lib.ss_clip_outcomes.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
+    # (counts, M, uniform_mix, cdf, prob, stream)
+    lib.ss_clip_sampling_cdf.argtypes = [vp, C.c_int32, C.c_double, vp, vp, vp]
     return lib
 
 

@@ -54,10 +54,12 @@ class PPOConfig:
     use_mini_batch: bool = False   # update: mini-batch epochs (agent_ppo.py:26-46): per epoch a permutation of the batch and floor(M / mini_batch_size) iterations of one critic step + one policy step
     mini_batch_size: int = 0       # rows per mini-batch (with use_mini_batch: >= 1, and at most the rollout's rows at update time)
     episode_stats: bool = False    # sampler: episode returns and lengths across rollouts, reward extremes and the means of the env's reward terms (learning/episode_stats.py)
+    clip_sampling: bool = False    # sampler, motion-imitation envs: per-clip failure counts on the device and the env's sampling CDF re-weighted by them after every rollout (learning/clip_sampling.py)
+    clip_sampling_mix: float = 0.1   # with clip_sampling: the share u of the uniform distribution in p = (1 - u) failures / sum + u / M (0 = the reference's update_sampling_prob)
     extra: dict = field(default_factory=dict)
 
 
-def _check_flags(c, device):
+def _check_flags(c, device, env=None):
     if c.deterministic_update and not c.mfma_update:
         raise ValueError("deterministic_update applies to the mfma_update path only (the torch update paths are reproducible as they are)")
     if c.fused_loss and device.type != "cuda":
@@ -72,16 +74,21 @@ def _check_flags(c, device):
         raise ValueError("use_mini_batch needs mini_batch_size >= 1")
     if c.extra.get("minibatch_gather", "kernel") not in ("kernel", "torch"):
         raise ValueError("extra['minibatch_gather'] is 'kernel' (ss_gather_rows) or 'torch'")
+    if c.clip_sampling:
+        if getattr(env, "motion_lib", None) is None or getattr(env, "motion_ids", None) is None:
+            raise ValueError("clip_sampling needs a motion-imitation env (one with motion_lib and motion_ids): there are no clips to weight")
+        if not 0.0 <= c.clip_sampling_mix <= 1.0:
+            raise ValueError("clip_sampling_mix must lie in [0, 1]")
 
 
 class AgentPPO:
-    fast_policy = fused_policy = fused_value = lib_norm = surrogate = value_mse = _shuffled = episode_stats = None   # the optional parts: None = off (also on an object that __init__ never saw)
+    fast_policy = fused_policy = fused_value = lib_norm = surrogate = value_mse = _shuffled = episode_stats = clip_outcomes = None   # the optional parts: None = off (also on an object that __init__ never saw)
 
     def __init__(self, env, cfg=None, seed=0):
         self.env, self.cfg = env, cfg or PPOConfig()
         c = self.cfg
         self.device = env.device
-        _check_flags(c, self.device)
+        _check_flags(c, self.device, env)
         torch.manual_seed(seed)
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed)
@@ -129,6 +136,11 @@ class AgentPPO:
             # episodes are counted from the resume point)
             from ..learning.episode_stats import EpisodeStats
             self.episode_stats = EpisodeStats(env.num_envs, self.device, getattr(env, "reward_part_names", ()))
+        if c.clip_sampling:
+            # the counters of the loaded clips live here, across rollouts; a checkpoint does not hold them: sync_to_host() hands them to the motion library, whose
+            # get_termination_history() is what is saved next to a checkpoint, as in the reference
+            from ..learning.clip_sampling import ClipOutcomes
+            self.clip_outcomes = ClipOutcomes(env.motion_lib, c.clip_sampling_mix)
 
     # ------------------------------------------------------------------ sampling
     def _prep_obs(self, obs):
@@ -166,6 +178,8 @@ class AgentPPO:
             a = mean if mean_action else mean + self.policy_net.action_log_std.exp() * noise
             act_row.copy_(a)
             a_env = self._prep_actions(a)
+        if buf["clip"] is not None:
+            buf["clip"][t, r].copy_(self.env.motion_ids[r])      # (clip_sampling; BEFORE the step: its launch overwrites the id of an env it re-initialises)
         obs, rew, died, timed_out, info = step_fn(a_env)
         buf["rewards"][t, r] = rew
         if buf["parts"] is not None:
@@ -183,7 +197,8 @@ class AgentPPO:
                     rewards=torch.empty(T, N, **f), dead=torch.empty(T, N, dtype=torch.bool, device=self.device),
                     done=torch.empty(T, N, dtype=torch.bool, device=self.device), a_env=torch.empty(N, self.action_dim, **f),
                     logp=torch.empty(T, N, 1, **f) if (self.fast_policy is not None and not mean_action) else None,
-                    parts=torch.empty(T, N, parts, **f) if parts else None)
+                    parts=torch.empty(T, N, parts, **f) if parts else None,
+                    clip=torch.empty(T, N, dtype=torch.int32, device=self.device) if self.clip_outcomes is not None else None)
 
     def _rollout_out(self, buf, last_obs_rows, mean_action):
         T, N = buf["rewards"].shape
@@ -201,6 +216,11 @@ class AgentPPO:
             out["episode_stats"] = self.episode_stats.update(out["rewards"], out["not_done"], buf["parts"])
             if buf["parts"] is not None:
                 out["reward_parts"] = buf["parts"]
+        if self.clip_outcomes is not None:
+            # two launches per rollout: the tally, then the env's sampling CDF rewritten in place — the next rollout's re-initialisations draw by the new weights
+            out["clip_ids"] = buf["clip"]
+            self.clip_outcomes.update(buf["clip"], buf["dead"], buf["done"])
+            self.clip_outcomes.apply()
         return out
 
     @torch.no_grad()
@@ -228,6 +248,8 @@ class AgentPPO:
         on the number of rows: the K order of the MFMA kernels is the same for every tile width).  Measured (profiles/r05_sampler.txt):
         no gain over the serial order at G = 2 and a loss at G >= 4 — a sub-batch's launch is as long as its heaviest env's chain
         whatever its size, two step kernels cannot share a CU's LDS, and the host issues G times the launches."""
+        if self.clip_outcomes is not None:
+            raise ValueError("clip_sampling: the pipelined sampler does not carry the motion-imitation env; use sample()")
         T, N, G = horizon or self.horizon, pipe.num_envs, pipe.sub_batches
         self.policy_net.eval()
         if getattr(self, "_pipe_obs", None) is None:
@@ -414,6 +436,8 @@ class AgentPPO:
         info["episodes_ended"] = (1.0 - batch["not_done"]).sum()
         if self.episode_stats is not None and "episode_stats" in batch:
             info.update(self.episode_stats.as_tensors(batch["episode_stats"]))   # the reference's names (LoggerRL), 0-dim tensors like every other value
+        if self.clip_outcomes is not None:
+            info.update(self.clip_outcomes.as_tensors())         # clips_failed, failed_episodes, completed_episodes, min_clip_prob, max_clip_prob
         return info
 
     def optimize_policy(self, epochs=1):

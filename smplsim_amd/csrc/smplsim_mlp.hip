@@ -1,6 +1,7 @@
 // smplsim_mlp.hip — host side of the policy MLP and the PPO update on gfx950: the launch planning of the bf16 GEMMs and the C ABI
 // (include/smplsim_mlp.h) of every learning entry point.  The kernels are in headers: ss_gemm128.h (128-row tiles, shared pieces),
-// ss_gemm256.h / ss_gemm256_kernels.h (256 x 256 tiles, weight gradient), ss_sampler.h, ss_ppo_head.h, ss_optim.h, ss_norm.h, ss_gather.h, ss_episode.h.
+// ss_gemm256.h / ss_gemm256_kernels.h (256 x 256 tiles, weight gradient), ss_sampler.h, ss_ppo_head.h, ss_optim.h, ss_norm.h, ss_gather.h, ss_episode.h,
+// ss_clip_sampling.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +19,7 @@
 #include "ss_norm.h"
 #include "ss_gather.h"
 #include "ss_episode.h"
+#include "ss_clip_sampling.h"
 
 namespace {
 
@@ -484,6 +486,26 @@ int ss_episode_stats(const float *rewards, const float *not_done, const float *p
   if (P == 4 && !(reinterpret_cast<size_t>(parts) & 15)) hipLaunchKernelGGL(episode::ss_episode_scan_kernel<true>, dim3((unsigned)G), dim3(episode::LANES), 0, st, a);
   else hipLaunchKernelGGL(episode::ss_episode_scan_kernel<false>, dim3((unsigned)G), dim3(episode::LANES), 0, st, a);
   hipLaunchKernelGGL(episode::ss_episode_reduce_kernel, dim3(1), dim3(episode::LANES), 0, st, static_cast<const double *>(a.part), G, W, (double)T * (double)N, stats);
+  return launched();
+}
+
+// ---- failure-weighted clip sampling (ss_clip_sampling.h): the tally of a rollout by integer atomics, one launch; the CDF of the failure counts, one workgroup
+int ss_clip_outcomes(const int32_t *clip_ids, const uint8_t *dead, const uint8_t *done, int32_t T, int32_t N, int32_t M, int64_t *counts, void *stream) {
+  if (!clip_ids || !dead || !done || !counts) return fail(SS_ERR_INVALID, "null argument");
+  if (T < 1 || N < 1 || M < 1) return fail(SS_ERR_INVALID, "ss_clip_outcomes: T >= 1, N >= 1, M >= 1");
+  if (reinterpret_cast<size_t>(counts) & 7) return fail(SS_ERR_INVALID, "ss_clip_outcomes: counts must be 8-byte aligned");
+  hipLaunchKernelGGL(clip_sampling::ss_clip_outcomes_kernel, dim3((unsigned)row_groups(N, clip_sampling::LANES)), dim3(clip_sampling::LANES), 0, (hipStream_t)stream,
+                     clip_ids, dead, done, T, N, M, reinterpret_cast<long long *>(counts));
+  return launched();
+}
+
+int ss_clip_sampling_cdf(const int64_t *counts, int32_t M, double uniform_mix, float *cdf, double *prob, void *stream) {
+  if (!counts || !cdf) return fail(SS_ERR_INVALID, "null argument");
+  if (M < 1) return fail(SS_ERR_INVALID, "ss_clip_sampling_cdf: M >= 1");
+  if (!(uniform_mix >= 0.0 && uniform_mix <= 1.0)) return fail(SS_ERR_INVALID, "ss_clip_sampling_cdf: uniform_mix must lie in [0, 1]");
+  const double keep = 1.0 - uniform_mix, floor_ = uniform_mix / (double)M, uniform = 1.0 / (double)M;   // each ONE fp64 operation, formed once, here
+  hipLaunchKernelGGL(clip_sampling::ss_clip_sampling_cdf_kernel, dim3(1), dim3(clip_sampling::CDF_THREADS), 0, (hipStream_t)stream,
+                     reinterpret_cast<const long long *>(counts), M, uniform, keep, floor_, cdf, prob);
   return launched();
 }
 

@@ -6,6 +6,7 @@
     python tools/train_ppo.py --task HumanoidSpeed --envs 4096 --epochs 5
     python tools/train_ppo.py --task HumanoidIm --envs 2048 --epochs 30      # motion imitation (synthetic clips unless --motion-file)
     python tools/train_ppo.py --task HumanoidIm --envs 2048 --mini-batch-size 8192   # six optimiser steps per epoch of the update instead of one
+    python tools/train_ppo.py --task HumanoidIm --envs 2048 --clip-sampling          # re-initialised envs draw the clips the policy still fails more often
 """
 import argparse
 import json
@@ -38,6 +39,8 @@ def main():
     ap.add_argument("--fused-norm", action="store_true", help="with --mfma-update: the policy's train-mode RunningNorm by the library's kernels and the networks' bf16 inputs made once (learning/fused_norm.py)")
     ap.add_argument("--mini-batch-size", type=int, default=0, help="update: mini-batch epochs of this many rows, the batch shuffled on the device once per epoch (0 = full-batch epochs; adds opt_steps to the log line)")
     ap.add_argument("--episode-stats", action="store_true", help="sampler: episode returns and lengths across rollouts and the means of the reward terms (learning/episode_stats.py; adds avg_episode_reward, avg_episode_len, ... to the log line, non-finite values left out)")
+    ap.add_argument("--clip-sampling", action="store_true", help="HumanoidIm: per-clip failure counts on the device, the env's sampling CDF re-weighted by them after every rollout (learning/clip_sampling.py; adds clips_failed, failed_episodes, completed_episodes, min_clip_prob, max_clip_prob to the log line)")
+    ap.add_argument("--clip-sampling-mix", type=float, default=0.1, metavar="U", help="with --clip-sampling: the share of uniform sampling in p = (1 - U) failures / sum + U / clips (0 = the reference's update_sampling_prob)")
     ap.add_argument("--save", default="")
     ap.add_argument("--log-every", type=int, default=1)
     ap.add_argument("--motion-file", default="", help="HumanoidIm: AMASS-style pickle ({key: {pose_aa, trans, fps}}); default = synthetic clips")
@@ -60,7 +63,8 @@ def main():
         env = SMPLSimVecEnv(args.envs, task=args.task, autoreset=True, seed=0)
     cfg = PPOConfig(hidden=tuple(int(x) for x in args.hidden.split(",")), min_batch_size=args.min_batch_size, opt_num_epochs=args.opt_epochs, amp_bf16=args.amp_bf16, mfma_inference=args.mfma_inference, mfma_update=args.mfma_update,
                     deterministic_update=args.deterministic_update, fused_loss=args.fused_loss, fused_optimizer=args.fused_optimizer, fused_norm=args.fused_norm,
-                    use_mini_batch=args.mini_batch_size > 0, mini_batch_size=args.mini_batch_size, episode_stats=args.episode_stats)
+                    use_mini_batch=args.mini_batch_size > 0, mini_batch_size=args.mini_batch_size, episode_stats=args.episode_stats,
+                    clip_sampling=args.clip_sampling, clip_sampling_mix=args.clip_sampling_mix)
     agent = AgentPPO(env, cfg, seed=0)
     ts, tu, n = 0.0, 0.0, 0
     for ep in range(args.epochs):
@@ -91,6 +95,9 @@ def main():
                           env.evaluate(lambda o: agent._prep_actions(agent.policy_net.select_action(agent._prep_obs(o), True))).items()}}))
         print(json.dumps({"eval": "PD clip replay (no policy)", **{k: round(v, 3) if isinstance(v, float) else v for k, v in env.evaluate().items()}}))
     if args.save:
+        if args.clip_sampling:                                  # the one read-back of the counters: the library's termination history, as the reference saves it next to a checkpoint
+            agent.clip_outcomes.sync_to_host()
+            torch.save(env.motion_lib.get_termination_history(), args.save + ".termination_history")
         torch.save(agent.get_full_state_weights(), args.save)
 
 
