@@ -1030,16 +1030,23 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
     fresh();
     typename HT::type h = HT::view(k->h);
     const typename HT::tree_type hc = HT::tree(k->hc);
+    // All 64 lanes run every level's loads and arithmetic; only the stores and the inputs of the group sums know which lanes hold
+    // nothing.  A group without a node (g >= nk: SMPL's levels are 2 4 5 4 4 4 nodes wide) redoes the level's LAST node — its record
+    // index is clamped — and a node's lanes 6, 7 redo row 5: every address is one a real lane reads, no lane reads what another
+    // writes before the next sync, and sum8 adds inside a group of 8 only, so what such lanes compute reaches nobody.  (Under
+    // per-lane conditions with zero defaults for the lanes that fail them a quarter of a level was moves and exec-mask bookkeeping.)
     const int r_ = lane & 7, g = lane >> 3;
-    int off[6];                                              // packed-symmetric offsets of row r_
+    const bool has_row = r_ < 6;
+    const int rr = has_row ? r_ : 5;
+    int off[6];                                              // packed-symmetric offsets of row rr
 #pragma unroll
-    for (int c = 0; c < 6; c++) { const int lo = r_ < c ? r_ : c, hi = r_ < c ? c : r_; off[c] = (lo * (11 - lo)) / 2 + hi; }
+    for (int c = 0; c < 6; c++) { const int lo = rr < c ? rr : c, hi = rr < c ? c : rr; off[c] = (lo * (11 - lo)) / 2 + hi; }
     SS_FT0();
     const unsigned long long nk0 = hc.nkpack[0], nk1 = hc.nkpack[1];
     auto NKC = [&](int L) { return (int)((((L - 1) < 16 ? nk0 : nk1) >> (4 * ((L - 1) & 15))) & 15ull) + 1; };   // nodes of level L >= 1
     // the free joint's right-hand side as a force on body 0 (row r_):  (S_fb b_fb)_r = R b_rot (angular rows; node 1's S holds the
     // columns of R) ; b_trans (linear rows)
-    auto fb_force = [&]() { return r_ < 3 ? S[18 + r_] * x[3] + S[24 + r_] * x[4] + S[30 + r_] * x[5] : x[r_ - 3]; };
+    auto fb_force = [&]() { return rr < 3 ? S[18 + rr] * x[3] + S[24 + rr] * x[4] + S[30 + rr] * x[5] : x[rr - 3]; };
     int s0 = h.nb - 1;                                        // records of level L start at s0(L) = (nodes of the levels before it)
     // 1:1 stretches of the tree (limbs: every node of level L has at most one child, and it sits in the same slot of level L + 1 —
     // ss_tables.h orders the levels for that and reports the levels as a bit mask, a constant of the fixed-layout instantiations): the
@@ -1064,21 +1071,20 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
       real row[NPASS][6], pa[NPASS], Ur[NPASS][3], red[NPASS][9];
       int nod[NPASS], jnt[NPASS];
       real sg[NPASS];
+      bool stores[NPASS];                                     // the lanes that hold a row of a node of this level
 #pragma unroll
       for (int ps = 0; ps < NPASS; ps++) {                    // ---- part 1: articulated row, U_r = IA_r S_j, partial S_j^T U
-        const int kk = ps * 8 + g;
-        nod[ps] = -1; jnt[ps] = 0;
         if (ps > 0 && ps * 8 >= nk) continue;                 // wave-uniform: a level of <= 8 nodes runs one pass (SMPL-X: 4 of 7 levels)
-#pragma unroll
-        for (int t = 0; t < 9; t++) red[ps][t] = 0.f;
-        if (r_ < 6 && kk < nk) {
+        const int kk = ps * 8 + g < nk - 1 ? ps * 8 + g : nk - 1;
+        stores[ps] = has_row && ps * 8 + g < nk;
+        {
           const int e0 = ti(hc.o_lev, 2 * (s0 + kk)), e1 = ti(hc.o_lev, 2 * (s0 + kk) + 1);
           const int b = e0 & 255, jn = (e0 >> 8) & 255, cfirst = e1 & 255, cc = (e1 >> 8) & 255;
           // (a constant of the unrolled level: only the levels between the tree's root and the kinematic root hold negated joints)
           const bool lev_neg = !HT::fixed || L > 32 || ((hc.neg >> (L - 1)) & 1ull);
           const real sgn = (lev_neg && ((e0 >> 24) & 1)) ? real(-1) : real(1);
           nod[ps] = b; jnt[ps] = jn; sg[ps] = sgn;
-          real rw[6], pv = pb[6 * b + r_];
+          real rw[6], pv = pb[6 * b + rr];
           if (!HT::fixed || L == hc.pel_level)               // (a constant of the unrolled level: the test is compiled into body 0's level only)
             if ((e0 >> 25) & 1) pv -= fb_force();
           const real *ao = Aown + h.a_stride * b;
@@ -1088,21 +1094,25 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
           const real *sn = S + 18 * jn;
 #pragma unroll
           for (int t = 0; t < 18; t++) sv[t] = sn[t];
-          const real sr0 = sn[r_], sr1 = sn[6 + r_], sr2 = sn[12 + r_];   // row r of S_j (the sign of S' cancels in U D^-1 U^T and in D)
+          // row r of S_j (the sign of S' cancels in U D^-1 U^T and in D); +0 in the lanes without a row: see the group sums below
+          // (loaded by every lane, then selected: a load inside the conditional expression is a branch around it)
+          const real sl0 = sn[rr], sl1 = sn[6 + rr], sl2 = sn[12 + rr];
+          const real sr0 = has_row ? sl0 : 0.f, sr1 = has_row ? sl1 : 0.f, sr2 = has_row ? sl2 : 0.f;
           auto add_child = [&](int j) {
-            const real *src = prev + ((cfirst + j) * 6 + r_) * 8;
+            const real *src = prev + ((cfirst + j) * 6 + rr) * 8;
             const float4_t v0 = ld4(src), v1 = ld4(src + 4);
             rw[0] += v0.x; rw[1] += v0.y; rw[2] += v0.z; rw[3] += v0.w; rw[4] += v1.x; rw[5] += v1.y; pv += v1.z;
           };
           if constexpr (HT::fixed) {                         // the most children of a node of this level is a constant of the unrolled level:
             const int cm = (int)((hc.cpack >> (3 * (L - 1))) & 7ull);   // predicated adds instead of a lane-varying loop (none on the leaf level)
             if (chain_in) {
-              // one 1:1 stretch that runs out at the leaf level (SMPL): a slot's registers are zero unless its child wrote them — children
-              // sit in their parent's slot, nothing deeper writes the slot of a leaf — so "has a child" need not be tested.  With two
+              // one 1:1 stretch that runs out at the leaf level (SMPL): children sit in their parent's slot, so where the next level is
+              // as wide as this one (a constant of the unrolled level) every node has its child and "has a child" need not be tested.
+              // Where it is narrower, the registers of the slots past it hold what a padding group left there: test.  With two
               // stretches (SMPL-X: fingers, trunk) the finger levels' registers are still live at the trunk's: test.
               constexpr unsigned long long ch_ = decltype(hc)::chain, run_ = ch_ ? ch_ / (ch_ & (~ch_ + 1ull)) : 0ull;
               constexpr bool one_run = ch_ != 0ull && (run_ & (run_ + 1ull)) == 0ull && (ch_ >> (decltype(hc)::nlev - 2)) == 1ull;
-              if (one_run || cc) {
+              if ((one_run && NKC(L + 1) == nk) || cc) {
 #pragma unroll
                 for (int c = 0; c < 6; c++) rw[c] += carry[ps][c];
                 pv += carry[ps][6];
@@ -1119,15 +1129,22 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
             real acc = 0.f;
 #pragma unroll
             for (int c = 0; c < 6; c++) acc += rw[c] * sv[6 * j + c];
-            Ur[ps][j] = acc;
+            Ur[ps][j] = has_row ? acc : 0.f;
           }
 #pragma unroll
           for (int c = 0; c < 6; c++) row[ps][c] = rw[c];
-          pa[ps] = pv;
-          st4w(Ubuf + (kk * 6 + r_) * 4, Ur[ps][0], Ur[ps][1], Ur[ps][2], pv);
-          red[ps][0] = sr0 * Ur[ps][0]; red[ps][1] = sr1 * Ur[ps][0]; red[ps][2] = sr1 * Ur[ps][1];
-          red[ps][3] = sr2 * Ur[ps][0]; red[ps][4] = sr2 * Ur[ps][1]; red[ps][5] = sr2 * Ur[ps][2];
-          red[ps][6] = sr0 * pv; red[ps][7] = sr1 * pv; red[ps][8] = sr2 * pv;
+          // the nine products below are all of lanes 6, 7 that enters a real lane's sum: both factors are selected to +0 there (a product
+          // with one zero factor takes the sign, or the NaN, of the other), so the sum is the one over the six rows, bit for bit
+          pa[ps] = pv = has_row ? pv : 0.f;
+          if (stores[ps]) st4w(Ubuf + (kk * 6 + rr) * 4, Ur[ps][0], Ur[ps][1], Ur[ps][2], pv);
+          {
+            // rounded products, as they were when a branch stood between them and the sums: in one basic block with sum8 the compiler
+            // contracts a product and the sum's first add into an fma (other bits, and a DPP move plus an fma for one DPP add)
+#pragma clang fp contract(off)
+            red[ps][0] = sr0 * Ur[ps][0]; red[ps][1] = sr1 * Ur[ps][0]; red[ps][2] = sr1 * Ur[ps][1];
+            red[ps][3] = sr2 * Ur[ps][0]; red[ps][4] = sr2 * Ur[ps][1]; red[ps][5] = sr2 * Ur[ps][2];
+            red[ps][6] = sr0 * pv; red[ps][7] = sr1 * pv; red[ps][8] = sr2 * pv;
+          }
         }
       }
       SS_FTICK(PF_F_P13);
@@ -1141,8 +1158,8 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
 #pragma unroll
       for (int ps = 0; ps < NPASS; ps++) {                    // ---- part 2: joint-space 3x3 algebra, rows handed towards the root
         if (ps > 0 && ps * 8 >= nk) continue;
-        const int kk = ps * 8 + g, b = nod[ps], jn = jnt[ps];
-        if (b >= 0) {
+        const int kk = ps * 8 + g < nk - 1 ? ps * 8 + g : nk - 1, b = nod[ps], jn = jnt[ps];
+        {
           float4_t U[6];
 #pragma unroll
           for (int c = 0; c < 6; c++) U[c] = ld4(Ubuf + (kk * 6 + c) * 4);
@@ -1160,7 +1177,7 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
 #pragma unroll
           for (int c = 0; c < 6; c++) rn[c] = row[ps][c] - (w0 * U[c].x + w1 * U[c].y + w2 * U[c].z);
           real pn = pa[ps] + a0 * y0 + a1 * y1 + a2 * y2;
-          real yr = r_ == 0 ? y0 : (r_ == 1 ? y1 : y2);
+          real yr = rr == 0 ? y0 : (rr == 1 ? y1 : y2);
           if constexpr (SELFCOL) {
             // a joint of the coupled set is not eliminated: its body's composite rows pass unchanged (as through a locked joint), and
             // what the dense system needs of it — U = IC S and the bias force — takes the (W, y) slot of the body
@@ -1170,15 +1187,18 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
               pn = pa[ps]; w0 = a0; w1 = a1; w2 = a2; yr = pa[ps];
             }
           }
-          if (chain_out) {
+          if (chain_out) {                                   // (registers, per lane: what a lane without a row leaves here reaches nobody)
 #pragma unroll
             for (int c = 0; c < 6; c++) carry[ps][c] = rn[c];
             carry[ps][6] = pn;
-          } else {
-            real *dst = cur + (kk * 6 + r_) * 8;
-            st4w(dst, rn[0], rn[1], rn[2], rn[3]); st4w(dst + 4, rn[4], rn[5], pn, 0.f);
           }
-          st4w(Wst + (b * 6 + r_) * 4, w0, w1, w2, yr);
+          if (stores[ps]) {
+            if (!chain_out) {
+              real *dst = cur + (kk * 6 + rr) * 8;
+              st4w(dst, rn[0], rn[1], rn[2], rn[3]); st4w(dst + 4, rn[4], rn[5], pn, 0.f);
+            }
+            st4w(Wst + (b * 6 + rr) * 4, w0, w1, w2, yr);
+          }
         }
       }
       SS_FTICK(PF_F_P2);
@@ -1311,46 +1331,37 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
 #pragma unroll
       for (int ps = 0; ps < NPASS; ps++) {
         if (ps > 0 && ps * 8 >= nk) continue;
-        const int kk = ps * 8 + g;
-        // (only the inputs of the group sums are initialised for the lanes without a row: everything else is read under `active` only —
-        //  a default for each of them was a move per value and level)
-        const bool active = r_ < 6 && kk < nk;
-#if defined(__HIPCC__)
-        int b, jn, pel = 0;
-        real p0 = 0.f, p1 = 0.f, p2 = 0.f, apr, s_0, s_1, s_2, nsg;
-#else                                                         // (the host compiler cannot see that the reads are guarded)
-        int b = -1, jn = 0, pel = 0;
-        real p0 = 0.f, p1 = 0.f, p2 = 0.f, apr = 0.f, s_0 = 0.f, s_1 = 0.f, s_2 = 0.f, nsg = 0.f;
-#endif
-        if (active) {
-          const int e0 = ti(hc.o_lev, 2 * (s0 + kk)), en = (e0 >> 16) & 255;
-          b = e0 & 255; jn = (e0 >> 8) & 255; pel = (e0 >> 25) & 1;
-          const bool lev_neg = !HT::fixed || L > 32 || ((hc.neg >> (L - 1)) & 1ull);
-          const real sgn = (lev_neg && ((e0 >> 24) & 1)) ? real(-1) : real(1);
-          const float4_t wr = ld4(Wst + (b * 6 + r_) * 4);
-          const real *sn = S + 18 * jn + r_;
-          s_0 = sn[0]; s_1 = sn[6]; s_2 = sn[12]; nsg = -sgn;
-          apr = chain_dn ? accp[ps] : An[8 * (en + 1) + r_];
-          p0 = wr.x * apr - (r_ == 0 ? wr.w : 0.f); p1 = wr.y * apr - (r_ == 1 ? wr.w : 0.f); p2 = wr.z * apr - (r_ == 2 ? wr.w : 0.f);
-        }
+        // (as towards the root: a group without a node redoes the level's last one, lanes 6, 7 redo row 5, and nothing but the stores
+        //  and the inputs of the group sums is guarded)
+        const int kk = ps * 8 + g < nk - 1 ? ps * 8 + g : nk - 1;
+        const bool stores = has_row && ps * 8 + g < nk;
+        const int e0 = ti(hc.o_lev, 2 * (s0 + kk)), en = (e0 >> 16) & 255;
+        const int b = e0 & 255, jn = (e0 >> 8) & 255, pel = (e0 >> 25) & 1;
+        const bool lev_neg = !HT::fixed || L > 32 || ((hc.neg >> (L - 1)) & 1ull);
+        const real sgn = (lev_neg && ((e0 >> 24) & 1)) ? real(-1) : real(1);
+        const float4_t wr = ld4(Wst + (b * 6 + rr) * 4);
+        const real *sn = S + 18 * jn + rr;
+        const real s_0 = sn[0], s_1 = sn[6], s_2 = sn[12], nsg = -sgn;
+        const real apr = chain_dn ? accp[ps] : An[8 * (en + 1) + rr];
+        real p0 = wr.x * apr - (rr == 0 ? wr.w : 0.f), p1 = wr.y * apr - (rr == 1 ? wr.w : 0.f), p2 = wr.z * apr - (rr == 2 ? wr.w : 0.f);
+        p0 = has_row ? p0 : 0.f; p1 = has_row ? p1 : 0.f; p2 = has_row ? p2 : 0.f;   // the sum is the one over the six rows
         p0 = w->sum8(p0); p1 = w->sum8(p1); p2 = w->sum8(p2);   // = -z = -sgn q''_j in every lane of the group
-        real acc = 0.f;
-        if (active) {
-          if constexpr (SELFCOL) {                             // a coupled joint's z is the dense system's
-            if ((cmask >> b) & 1ull) { p0 = -this->zb[3 * b]; p1 = -this->zb[3 * b + 1]; p2 = -this->zb[3 * b + 2]; }
-          }
-          acc = apr - (s_0 * p0 + s_1 * p1 + s_2 * p2);
-          An[8 * (b + 1) + r_] = acc;
-          accp[ps] = acc;
-          if (r_ < 3) x[3 * jn + r_] = nsg * (r_ == 0 ? p0 : (r_ == 1 ? p1 : p2));
+        if constexpr (SELFCOL) {                               // a coupled joint's z is the dense system's
+          if ((cmask >> b) & 1ull) { p0 = -this->zb[3 * b]; p1 = -this->zb[3 * b + 1]; p2 = -this->zb[3 * b + 2]; }
+        }
+        const real acc = apr - (s_0 * p0 + s_1 * p1 + s_2 * p2);
+        accp[ps] = acc;
+        if (stores) {
+          An[8 * (b + 1) + rr] = acc;
+          if (rr < 3) x[3 * jn + rr] = nsg * (rr == 0 ? p0 : (rr == 1 ? p1 : p2));
         }
         if (pel_level) {                                       // body 0 reached: the free joint's solution from its acceleration
           real t0 = 0.f, t1 = 0.f, t2 = 0.f;                  // R^T a_ang: lane r < 3 holds component r of a_ang
-          if (pel && r_ < 3) { t0 = S[18 + r_] * acc; t1 = S[24 + r_] * acc; t2 = S[30 + r_] * acc; }
+          if (pel && rr < 3) { t0 = S[18 + rr] * acc; t1 = S[24 + rr] * acc; t2 = S[30 + rr] * acc; }
           t0 = w->sum8(t0); t1 = w->sum8(t1); t2 = w->sum8(t2);
-          if (pel) {
-            if (r_ >= 3 && r_ < 6) x[r_ - 3] = acc;             // x_trans = a_lin
-            else if (r_ < 3) x[3 + r_] = r_ == 0 ? t0 : (r_ == 1 ? t1 : t2);
+          if (pel && stores) {
+            if (rr >= 3) x[rr - 3] = acc;                       // x_trans = a_lin
+            else x[3 + rr] = rr == 0 ? t0 : (rr == 1 ? t1 : t2);
           }
         }
       }
