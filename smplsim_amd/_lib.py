@@ -39,9 +39,7 @@ class ExtensionMissing(RuntimeError):
 
 def build(verbose=False, force=False):
     """hipcc --offload-arch=gfx950 build of the kernels + C ABI (cross-compiles without a GPU)."""
-    srcs = [os.path.join(SRC_DIR, f) for f in ("smplsim_hip.hip", "smplsim_hip_sc.hip", "smplsim_hip_im.hip", "smplsim_motion.hip", "smplsim_mlp.hip", "smplsim_hip_x.hip", "ss_env_kernel.h", "ss_kernel.h", "ss_selfcol.h", "ss_api.h", "ss_tables.h", "ss_hdr.h",
-                                                  "ss_motion.h", "ss_motion_api.h", "ss_wave_gpu.h", "ss_imfused.h", "ss_mjcf.h", "ss_gemm128.h", "ss_gemm256.h", "ss_gemm256_kernels.h", "ss_sampler.h", "ss_ppo_head.h", "ss_optim.h", "ss_norm.h", "ss_gather.h", "ss_episode.h", "ss_clip_sampling.h")]
-    srcs += [os.path.join(os.path.dirname(_PKG), "include", h) for h in ("smplsim_hip.h", "smplsim_motion.h", "smplsim_mlp.h")]
+    deps = _sources()                                        # every source file: an edit to any of them rebuilds the library
     opt = os.environ.get("SS_HIPCC_OPT", DEFAULT_OPT).split()
     scopt = os.environ.get("SS_HIPCC_SC_OPT", SC_OPT).split()
     mopt = os.environ.get("SS_HIPCC_MOTION_OPT", MOTION_OPT).split()
@@ -49,12 +47,14 @@ def build(verbose=False, force=False):
     stamp = LIB_PATH + ".flags"                              # rebuild when the flags change, not only the sources
     flag_str = " ".join(opt + ["|"] + scopt + ["|"] + mopt + ["|"] + xopt)
     same_flags = os.path.exists(stamp) and open(stamp).read() == flag_str
-    if not force and same_flags and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
+    if not force and same_flags and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in deps):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objs, procs = [], []
-    for src, flags in ((srcs[0], opt), (srcs[1], scopt), (srcs[2], opt), (srcs[3], mopt), (srcs[4], mopt), (srcs[5], xopt)):   # stepper (4 units), motion library, policy MLP: their own
-        obj = os.path.join(_PKG, os.path.basename(src).replace(".hip", ".o"))   # flags, compiled side by side
+    units = (("smplsim_hip.hip", opt), ("smplsim_hip_sc.hip", scopt), ("smplsim_hip_im.hip", opt), ("smplsim_motion.hip", mopt),
+             ("smplsim_mlp.hip", mopt), ("smplsim_hip_x.hip", xopt))   # stepper (4 units), motion library, policy MLP: their own flags,
+    for unit, flags in units:                                          # compiled side by side
+        src, obj = os.path.join(SRC_DIR, unit), os.path.join(_PKG, unit.replace(".hip", ".o"))
         cmd = [hipcc, "--offload-arch=gfx950", *flags, "-std=c++17", "-fPIC", "-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd))
@@ -74,17 +74,20 @@ def build(verbose=False, force=False):
     return LIB_PATH
 
 
+def _sources():
+    """Every .h / .hip file under csrc/ and include/, sorted: what the library is built from and what source_hash() covers."""
+    inc = os.path.join(os.path.dirname(_PKG), "include")
+    return [os.path.join(d, f) for d in (SRC_DIR, inc) for f in sorted(os.listdir(d)) if f.endswith((".h", ".hip"))]
+
+
 def source_hash():
     """What a profile / counter summary was taken on: sha256 (16 hex digits) over every file under smplsim_amd/csrc and include/
     plus the compiler flags of the three groups of translation units.  tools/prof_summarize.py stores it in profiles/pmc_summary_*.json,
     bench.py recomputes it and refuses counter blocks of another tree (roofline.pmc_stale)."""
     import hashlib
     h = hashlib.sha256()
-    inc = os.path.join(os.path.dirname(_PKG), "include")
-    for d in (SRC_DIR, inc):
-        for f in sorted(os.listdir(d)):
-            if f.endswith((".h", ".hip")):
-                h.update(f.encode()); h.update(open(os.path.join(d, f), "rb").read())
+    for path in _sources():
+        h.update(os.path.basename(path).encode()); h.update(open(path, "rb").read())
     h.update(" ".join([os.environ.get("SS_HIPCC_OPT", DEFAULT_OPT), "|", os.environ.get("SS_HIPCC_SC_OPT", SC_OPT), "|",
                        os.environ.get("SS_HIPCC_MOTION_OPT", MOTION_OPT), "|", os.environ.get("SS_HIPCC_X_OPT", X_OPT)]).encode())
     return h.hexdigest()[:16]

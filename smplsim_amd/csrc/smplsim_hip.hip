@@ -10,7 +10,6 @@
 
 namespace {
 
-
 // GAE: one lane per env column, time loop backwards; every [t, :] row access is coalesced across the wave.  HBM bound
 // and tiny (5 arrays of T*N floats), it only exists so that the rollout never leaves the device.
 __global__ void ss_gae_kernel(const float *rew, const float *nd, const float *ndead, const float *val, const float *boot,
@@ -69,28 +68,28 @@ __global__ void __launch_bounds__(1024) ss_order_kernel(const int32_t *keys, int
   for (int i = threadIdx.x; i < n; i += blockDim.x) { int key = keys[i]; key = key < 0 ? 0 : (key > 1023 ? 1023 : key); order[atomicAdd(&offs[1023 - key], 1)] = i; }
 }
 
-
 typedef ss::kern_t kern_t;
 // instantiations per model size: plain (the headline), +body-frame outputs, +per-env body shapes (which includes the outputs)
 // The two fixtures' sizes get instantiations with compile-time dimensions and LDS layout (HdrFixedT, ss_hdr.h): -2.4% per step
 // launch on the SMPL headline (profiles/r02b_variants.txt); any other model of a variant's size class runs the generic one.
-kern_t pick_kernel(int variant, int flavour, const ss::Hdr &h, const ss::HdrC &hc) {
+kern_t pick_kernel(const ss::KernelKey &key, const ss::Hdr &h, const ss::HdrC &hc) {
+  const bool plain = !key.selfcol && !key.imit;              // (what this unit instantiates)
 #ifndef SS_NO_FIXED_LAYOUT
-  if (variant == 0 && flavour == 0 && HdrSmpl::matches(h, hc)) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, false, false, HdrSmpl>;
+  if (key.variant == 0 && !key.bodyout && HdrSmpl::matches(h, hc)) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, false, false, HdrSmpl>;
 #ifndef SS_ONLY_HEADLINE
-  if (variant == 0 && flavour == 1 && HdrSmpl::matches(h, hc)) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, false, HdrSmpl>;
-  if (variant == 0 && flavour == 2 && HdrSmpl::matches(h, hc)) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, true, HdrSmpl>;   // per-env body shapes
+  if (key.variant == 0 && plain && key.bodyout && !key.shaped && HdrSmpl::matches(h, hc)) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, false, HdrSmpl>;
+  if (key.variant == 0 && plain && key.shaped && HdrSmpl::matches(h, hc)) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, true, HdrSmpl>;   // per-env body shapes
 #endif
 #endif
-  if (variant == 0 && flavour == 0) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, false, false>;
+  if (key.variant == 0 && !key.bodyout) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, false, false>;
 #ifndef SS_ONLY_HEADLINE                                     // (experiment builds, tools/build_variant.sh, keep the headline kernel alone)
-  if (flavour == 3 || flavour == 5 || flavour == 7) return ss::pick_kernel_selfcol(variant, flavour == 5, flavour == 7, h, hc);   // smplsim_hip_sc.hip
-  if (flavour == 4 || flavour == 6) return ss::pick_kernel_imitation(variant, flavour == 6, h, hc);                          // smplsim_hip_im.hip
-  if (variant == 0) {                                        // SMPL layout (24 bodies)
-    if (flavour == 1) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, false>;
+  if (key.selfcol) return key.imit ? ss::pick_kernel_imitation_selfcol(key, h, hc) : ss::pick_kernel_selfcol(key, h, hc);
+  if (key.imit) return ss::pick_kernel_imitation(key, h, hc);
+  if (key.variant == 0) {                                    // SMPL layout (24 bodies)
+    if (!key.shaped) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, false>;
     return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, true>;
   }
-  if (variant == 1) return ss::pick_kernel_x(flavour, h, hc);   // SMPL-X/H layout (52 bodies): smplsim_hip_x.hip
+  if (key.variant == 1) return ss::pick_kernel_x(key, h, hc);   // SMPL-X/H layout (52 bodies)
 #endif
   return nullptr;
 }
@@ -102,6 +101,7 @@ struct HipBackend {
   static bool set_device(int d) { return hipSetDevice(d) == hipSuccess; }
   static bool download(void *dst, const void *src, size_t n) { return hipMemcpy(dst, src, n, hipMemcpyDeviceToHost) == hipSuccess; }
   static bool copy_d2d(void *dst, const void *src, size_t n, void *stream) { return hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess; }
+  static const char *hip_err() { hipError_t e = hipGetLastError(); return e == hipSuccess ? nullptr : hipGetErrorString(e); }
   static int lds_capacity() { return 160 * 1024; }
   static int num_cus() { int d = 0, n = 256; if (hipGetDevice(&d) == hipSuccess) { hipDeviceProp_t p; if (hipGetDeviceProperties(&p, d) == hipSuccess) n = p.multiProcessorCount; } return n; }
   static int max_waves(int variant, int selfcol) { return (variant == 0 ? (selfcol ? SS_MAX_THREADS_SC : SS_MAX_THREADS) : SS_MAX_THREADS_X) / 64; }
@@ -109,53 +109,35 @@ struct HipBackend {
     const int n = st.num_envs;
     hipLaunchKernelGGL(ss_key_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, st.qvel, st.qacc_warm, st.touch, st.solver_iters, nv, n, key);
     hipLaunchKernelGGL(ss_order_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, key, order, n);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? nullptr : hipGetErrorString(e);
+    return hip_err();
   }
   static const char *gae(const float *rew, const float *nd, const float *ndead, const float *val, const float *boot, int T, int N,
                          float gamma, float tau, float *adv, float *ret, void *stream) {
     hipLaunchKernelGGL(ss_gae_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, rew, nd, ndead, val, boot, T, N, gamma, tau, adv, ret);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? nullptr : hipGetErrorString(e);
+    return hip_err();
   }
   static int &regs_ref() { static thread_local int r = 0; return r; }
   static int kernel_regs() { return regs_ref(); }
+  struct Configured { kern_t kern; size_t lds; int regs; };   // a kernel whose dynamic-LDS limit is set: to how much, and its VGPRs
   static const char *launch(const ss::KArgs &k, int nenv, int envs_per_wg, size_t lds_bytes, void *stream, int fixed_epw, int max_wgs) {
-    const bool bodyout = (k.out0 || k.power) && (k.mode == ss::MODE_STEP || k.mode == ss::MODE_RESET);
-    const int flavour = k.im ? (k.cfg.self_collision ? 7 : (k.st.shape_id ? 6 : 4)) : (k.cfg.self_collision ? (k.st.shape_id ? 5 : 3) : (k.st.shape_id ? 2 : (bodyout ? 1 : 0)));
-    kern_t kern = pick_kernel(ss::kernel_variant(k.h), flavour, k.h, k.hc);
+    kern_t kern = pick_kernel(ss::kernel_key(k), k.h, k.hc);
     if (!kern) return "no kernel variant for this model size";
-    static thread_local kern_t configured[32] = {};
-    static thread_local size_t configured_lds[32] = {};
-    static thread_local int regs_by_slot[32] = {};            // VGPRs per instantiation: launch_info reports the LAUNCHED kernel's
-    const int slot = 16 * ss::kernel_variant(k.h) + flavour;
-    if (configured[slot] != kern || configured_lds[slot] < lds_bytes) {
+    static thread_local std::vector<Configured> configured;   // a few entries, searched in order
+    auto c = std::find_if(configured.begin(), configured.end(), [&](const Configured &x) { return x.kern == kern; });
+    if (c == configured.end()) c = configured.insert(c, Configured{kern, 0, 0});
+    if (c->lds < lds_bytes) {
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
       if (e != hipSuccess) return hipGetErrorString(e);
       hipFuncAttributes fa;
-      if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kern)) == hipSuccess) regs_by_slot[slot] = fa.numRegs;
-      configured[slot] = kern; configured_lds[slot] = lds_bytes;
+      if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kern)) == hipSuccess) c->regs = fa.numRegs;
+      c->lds = lds_bytes;
     }
-    regs_ref() = regs_by_slot[slot];                          // of this launch (ss_api::run copies it into the batch)
+    regs_ref() = c->regs;                                     // of this launch (ss_api::run copies it into the batch)
     static thread_local int cus = num_cus();
-    // small batches: spread the envs over all CUs instead of filling a third of them with full workgroups — a wave that
-    // shares its CU with 3 others runs ~13% faster than one of 12 (1024 envs: 1.27 -> 1.13 ms per step launch)
-    const int per_cu = (nenv + cus - 1) / cus;
-    if (fixed_epw > 0) {                                      // fixed by the caller (ss_set_launch_geometry)
-      envs_per_wg = fixed_epw;
-      lds_bytes = ss::launch_lds_bytes(k, envs_per_wg);
-    } else if (per_cu < envs_per_wg) {
-      envs_per_wg = per_cu < 1 ? 1 : per_cu;
-      lds_bytes = ss::launch_lds_bytes(k, envs_per_wg);
-    }
-    int wgs = (nenv + envs_per_wg - 1) / envs_per_wg;
-    const int resident = cus * (int)(lds_capacity() / lds_bytes > 0 ? lds_capacity() / lds_bytes : 1);
-    if (wgs > resident) wgs = resident;                      // persistent: one resident set of workgroups
-    if (max_wgs > 0 && wgs > max_wgs) wgs = max_wgs;         // the caller shares the GPU between concurrent batches
-    dim3 grid(wgs), block(64 * envs_per_wg);
-    hipLaunchKernelGGL(kern, grid, block, lds_bytes, (hipStream_t)stream, k);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? nullptr : hipGetErrorString(e);
+    const size_t lds_fixed = ss::launch_lds_bytes(k, 0);
+    const ss::LaunchGeometry g = ss::launch_geometry(nenv, cus, envs_per_wg, fixed_epw, max_wgs, lds_capacity(), lds_fixed, ss::launch_lds_bytes(k, 1) - lds_fixed);
+    hipLaunchKernelGGL(kern, dim3(g.wgs), dim3(64 * g.envs_per_wg), g.lds_bytes, (hipStream_t)stream, k);
+    return hip_err();
   }
 };
 

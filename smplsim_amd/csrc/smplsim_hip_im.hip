@@ -5,8 +5,9 @@
 
 namespace ss {
 
-kern_t pick_kernel_imitation(int variant, bool shaped, const Hdr &h, const HdrC &hc) {
-  if (shaped) {                                              // per-env body shapes (PHC-style: every env tracks clips with its own body)
+kern_t pick_kernel_imitation(const KernelKey &key, const Hdr &h, const HdrC &hc) {
+  const int variant = key.variant;
+  if (key.shaped) {                                              // per-env body shapes (PHC-style: every env tracks clips with its own body)
     if (variant == 0) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, true, HdrRuntime, false, true>;
     if (variant == 1) return ss_env_kernel<3, 3, 2, 2, SS_MAX_THREADS_X, true, true, HdrRuntime, false, true>;
     return nullptr;
@@ -24,8 +25,8 @@ kern_t pick_kernel_imitation(int variant, bool shaped, const Hdr &h, const HdrC 
 // observation row pointer between the top of the step pass and its use (hipcc 7.2: the value is spilled and comes back zero; seen as
 // an all-zero self observation in tests/test_gpu_parity.py::test_fused_imitation_step_with_body_body_contacts_on_gpu); the flags of
 // this unit compile it correctly.
-kern_t pick_kernel_imitation_selfcol(int variant, bool shaped, const Hdr &, const HdrC &) {
-  if (variant == 0 && !shaped) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS_SC, true, false, HdrRuntime, true, true>;
+kern_t pick_kernel_imitation_selfcol(const KernelKey &key, const Hdr &, const HdrC &) {
+  if (key.variant == 0 && !key.shaped) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS_SC, true, false, HdrRuntime, true, true>;
   return nullptr;
 }
 

@@ -4,9 +4,9 @@
 
 namespace ss {
 
-kern_t pick_kernel_selfcol(int variant, bool shaped, bool imit, const Hdr &h, const HdrC &hc) {
-  if (imit) return pick_kernel_imitation_selfcol(variant, shaped, h, hc);   // smplsim_hip_im.hip
-  if (shaped) {                                              // one geom table per body shape
+kern_t pick_kernel_selfcol(const KernelKey &key, const Hdr &h, const HdrC &hc) {
+  const int variant = key.variant;
+  if (key.shaped) {                                             // one geom table per body shape
     if (variant == 0) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS_SC, true, true, HdrRuntime, true>;
     if (variant == 1) return ss_env_kernel<3, 3, 2, 2, SS_MAX_THREADS_X, true, true, HdrRuntime, true>;
     return nullptr;

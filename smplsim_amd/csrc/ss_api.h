@@ -1,10 +1,14 @@
 // ss_api.h — host side of the C ABI (include/smplsim_hip.h), written once and instantiated with a
-// backend: the HIP backend in smplsim_hip.hip (the product) and the wavefront-emulator backend in
-// tests/wave_emu/emu.cpp (unit-test infrastructure).  A backend provides:
-//   static void *alloc(size_t);  static void free_(void *);  static bool upload(void *dst, const void *src, size_t);
-//   static int lds_capacity();   static int max_waves(int variant);   static const char *launch(const ss::KArgs &, int nenv, int envs_per_wg, size_t lds_bytes, void *stream, int fixed_envs_per_wg, int max_wgs);
-//   static bool set_device(int);
+// backend: the HIP backend in smplsim_hip.hip (the product), the wavefront-emulator backend in
+// tests/wave_emu/emu.cpp and the device-less one of tests/host_paths_check.cpp (unit-test infrastructure).
+// ss_api<BE> holds every check and every body; SS_DEFINE_C_API(BE) at the end of this file makes the extern "C" entries of them.  A backend provides:
+//   static void *alloc(size_t);  static void free_(void *);  static bool set_device(int);  static bool upload / download(void *dst, const void *src, size_t);
+//   static bool copy_d2d(void *dst, const void *src, size_t, void *stream);  static int lds_capacity();  static int max_waves(int variant, int selfcol);
+//   static const char *launch(const ss::KArgs &, int nenv, int envs_per_wg, size_t lds_bytes, void *stream, int fixed_envs_per_wg, int max_wgs);
+//   static int kernel_regs();   // of that launch;   order_by_key and gae (the hand-out order, GAE), which like launch return nullptr or an error string
+// launch picks the instantiation by ss::kernel_key(KArgs) and its grid by ss::launch_geometry (both ss_hdr.h).
 #pragma once
+#include <cassert>
 #include <cstdlib>
 #include <new>
 #include <string>
@@ -17,7 +21,7 @@ namespace ss {
 inline std::string &last_error() { static thread_local std::string e; return e; }
 inline std::string *&error_slot() { static thread_local std::string *p = nullptr; return p; }   // the handle the running entry works on
 struct HandleScope {                      // entries that take a handle also record their error message in it (ss_batch_last_error)
-  explicit HandleScope(std::string *slot) { error_slot() = slot; }
+  template <class H> explicit HandleScope(const H *handle) { error_slot() = handle ? &handle->err : nullptr; }
   ~HandleScope() { error_slot() = nullptr; }
 };
 }  // namespace ss
@@ -79,25 +83,26 @@ struct ss_api {
     ss_model *m = new (std::nothrow) ss_model();
     if (!m) return fail(SS_ERR_NOMEM, "out of host memory");
     if (!ss::build_host_model(*d, m->hm)) { std::string e = m->hm.error; delete m; return fail(SS_ERR_INVALID, e); }
+    return upload_model(m, device, m->hm.bodyc, m->hm.candc, m->hm.pairs, m->hm.geomc, out);
+  }
+  template <class T> static bool up(T *&dst, const std::vector<T> &v) {
+    const size_t bytes = v.size() * sizeof(T);
+    dst = static_cast<T *>(BE::alloc(bytes ? bytes : 4));
+    if (dst && bytes && !BE::upload(dst, v.data(), bytes)) { BE::free_(dst); dst = nullptr; }
+    return dst != nullptr;
+  }
+  // The one way a model gets its six device tables: the shared blob and candb from m->hm, the shape-dependent ones as given (one block
+  // per body shape), the per-body elimination-tree table of the SELFCOL kernels behind the pair table.  Hands m out, or frees it.
+  static int upload_model(ss_model *m, int device, const std::vector<ss::real> &bodyc, const std::vector<ss::real> &candc,
+                          std::vector<int32_t> pairs, const std::vector<ss::real> &geomc, ss_model **out) {
     m->device = device;
     if (!BE::set_device(device)) { delete m; return fail(SS_ERR_HIP, "cannot select device"); }
-    auto up = [&](const void *src, size_t bytes) -> void * {
-      void *p = BE::alloc(bytes ? bytes : 4);
-      if (p && bytes && !BE::upload(p, src, bytes)) { BE::free_(p); p = nullptr; }
-      return p;
-    };
-    m->d_shared = (uint32_t *)up(m->hm.shared.data(), m->hm.shared.size() * 4);
-    m->d_bodyc = (ss::real *)up(m->hm.bodyc.data(), m->hm.bodyc.size() * sizeof(ss::real));
-    m->d_candc = (ss::real *)up(m->hm.candc.data(), m->hm.candc.size() * sizeof(ss::real));
-    m->d_candb = (int32_t *)up(m->hm.candb.data(), m->hm.candb.size() * 4);
-    {
-      std::vector<int32_t> pt(m->hm.pairs);                  // pair table, then the per-body elimination-tree table of the SELFCOL kernels
-      m->hm.sc.o_sctab = (int)pt.size();
-      pt.insert(pt.end(), m->hm.sctab.begin(), m->hm.sctab.end());
-      m->d_pairs = (int32_t *)up(pt.data(), pt.size() * 4);
+    m->hm.sc.o_sctab = (int)pairs.size();
+    pairs.insert(pairs.end(), m->hm.sctab.begin(), m->hm.sctab.end());
+    if (!(up(m->d_shared, m->hm.shared) && up(m->d_bodyc, bodyc) && up(m->d_candc, candc) && up(m->d_candb, m->hm.candb) && up(m->d_pairs, pairs) && up(m->d_geomc, geomc))) {
+      model_destroy(m);                                      // (a table that failed is null: everything allocated so far is freed once)
+      return fail(SS_ERR_HIP, "device table upload failed");
     }
-    m->d_geomc = (ss::real *)up(m->hm.geomc.data(), m->hm.geomc.size() * sizeof(ss::real));
-    if (!m->d_shared || !m->d_bodyc || !m->d_candc || !m->d_candb || !m->d_pairs || !m->d_geomc) { model_destroy(m); return fail(SS_ERR_HIP, "device table upload failed"); }
     *out = m;
     return SS_OK;
   }
@@ -135,24 +140,8 @@ struct ss_api {
       pairs.insert(pairs.end(), hm.pairs.begin(), hm.pairs.end());
     }
     if (12 * m->hm.h_sc.nb > m->hm.h_sc.l_Wst - m->hm.h_sc.l_IA) { delete m; return fail(SS_ERR_LDS, "no room for the per-env body offsets"); }   // (the aliased layout has the 12 nb by construction)
-    m->device = device; m->num_shapes = num_shapes;
-    if (!BE::set_device(device)) { delete m; return fail(SS_ERR_HIP, "cannot select device"); }
-    auto up = [&](const void *src, size_t bytes) -> void * {
-      void *p = BE::alloc(bytes ? bytes : 4);
-      if (p && bytes && !BE::upload(p, src, bytes)) { BE::free_(p); p = nullptr; }
-      return p;
-    };
-    m->d_shared = (uint32_t *)up(m->hm.shared.data(), m->hm.shared.size() * 4);
-    m->d_bodyc = (ss::real *)up(bodyc.data(), bodyc.size() * sizeof(ss::real));
-    m->d_candc = (ss::real *)up(candc.data(), candc.size() * sizeof(ss::real));
-    m->d_candb = (int32_t *)up(m->hm.candb.data(), m->hm.candb.size() * 4);
-    m->hm.sc.o_sctab = (int)pairs.size();
-    pairs.insert(pairs.end(), m->hm.sctab.begin(), m->hm.sctab.end());
-    m->d_pairs = (int32_t *)up(pairs.data(), pairs.size() * 4);
-    m->d_geomc = (ss::real *)up(geomc.data(), geomc.size() * sizeof(ss::real));
-    if (!m->d_shared || !m->d_bodyc || !m->d_candc || !m->d_candb || !m->d_pairs || !m->d_geomc) { model_destroy(m); return fail(SS_ERR_HIP, "device table upload failed"); }
-    *out = m;
-    return SS_OK;
+    m->num_shapes = num_shapes;
+    return upload_model(m, device, bodyc, candc, std::move(pairs), geomc, out);
   }
   static void model_destroy(ss_model *m) {
     if (!m) return;
@@ -191,7 +180,7 @@ struct ss_api {
     int cap = BE::lds_capacity();
     const size_t pool_b = cfg->self_collision ? (size_t)ss::ss_pool_floats(m->hm.sc) * sizeof(ss::real) : 0;   // the workgroup's shared dense block
     int e = (int)((cap - (long)shared_b - (long)pool_b) / (long)env_b);
-    if (e < 1) { delete b; return fail(SS_ERR_LDS, "model does not fit in LDS"); }
+    if (e < 1) { batch_destroy(b); return fail(SS_ERR_LDS, "model does not fit in LDS"); }
     { const int mw = BE::max_waves(ss::kernel_variant(h), cfg->self_collision); if (e > mw) e = mw; }   // launch bound of the kernel variant
     { const char *cap = getenv("SS_ENVS_PER_WG"); if (cap && atoi(cap) > 0 && atoi(cap) < e) e = atoi(cap); }
     b->envs_per_wg = e;
@@ -200,10 +189,10 @@ struct ss_api {
     b->d_prof = (unsigned long long *)BE::alloc(64 * sizeof(unsigned long long));
     if (b->d_prof) { unsigned long long z[64] = {0}; BE::upload(b->d_prof, z, sizeof z); }
 #endif
-    if (!BE::set_device(m->device)) { delete b; return fail(SS_ERR_HIP, "cannot select device"); }   // the counter must live on the batch's GPU
+    if (!BE::set_device(m->device)) { batch_destroy(b); return fail(SS_ERR_HIP, "cannot select device"); }   // the counter must live on the batch's GPU
     b->d_counter = (int32_t *)BE::alloc(2 * sizeof(int32_t));
     const int32_t zeros[2] = {0, 0};
-    if (!b->d_counter || !BE::upload(b->d_counter, zeros, sizeof zeros)) { BE::free_(b->d_counter); delete b; return fail(SS_ERR_NOMEM, "device allocation failed"); }
+    if (!b->d_counter || !BE::upload(b->d_counter, zeros, sizeof zeros)) { batch_destroy(b); return fail(SS_ERR_NOMEM, "device allocation failed"); }
     *out = b;
     return SS_OK;
   }
@@ -226,6 +215,7 @@ struct ss_api {
   }
   static int run(const ss_batch *b, const ss::KArgs &k, void *stream) {
     if (!BE::set_device(b->m->device)) return fail(SS_ERR_HIP, "cannot select device");
+    assert(b->lds_bytes == ss::launch_lds_bytes(k, b->envs_per_wg));   // launch_geometry (ss_hdr.h) derives the launch's LDS bytes from the latter
     const char *err = BE::launch(k, b->st.num_envs, b->envs_per_wg, b->lds_bytes, stream, b->fixed_envs_per_wg, b->max_wgs);
     if (err) return fail(SS_ERR_HIP, err);
     b->kernel_regs = BE::kernel_regs();
@@ -244,19 +234,21 @@ struct ss_api {
   static int step(ss_batch *b, const float *actions, const float *task_rand, float *obs, float *reward, uint8_t *term,
                   uint8_t *trunc, void *stream) {
     if (!b || !actions || !obs || !reward || !term || !trunc) return fail(SS_ERR_INVALID, "null argument");
+    return run(b, step_args(b, actions, task_rand, obs, reward, term, trunc), stream);
+  }
+  // what the three step entries hand the kernel alike (the fused imitation step: reward and flags come from the imitation part)
+  static ss::KArgs step_args(const ss_batch *b, const float *actions, const float *task_rand, float *obs, float *reward, uint8_t *term, uint8_t *trunc) {
     ss::KArgs k = base_args(b, ss::MODE_STEP);
     k.actions = ss_batch::R(actions); k.task_rand = ss_batch::R(task_rand); k.obs = ss_batch::R(obs); k.reward = ss_batch::R(reward);
     k.terminated = term; k.truncated = trunc;
-    return run(b, k, stream);
+    return k;
   }
   static int step_autoreset(ss_batch *b, const float *actions, const float *task_rand, const float *reset_task_rand, float *obs,
                             float *obs_next, float *reward, uint8_t *term, uint8_t *trunc, void *stream) {
     if (!b || !actions || !obs || !obs_next || !reward || !term || !trunc) return fail(SS_ERR_INVALID, "null argument");
     if (b->cfg.state_init == SS_INIT_EXTERNAL) return fail(SS_ERR_INVALID, "in-launch autoreset: StateInit External has no reset state of its own");
     if (b->cfg.state_init == SS_INIT_FALL && !b->fall_actions) return fail(SS_ERR_INVALID, "in-launch Fall reset needs ss_set_fall_actions");
-    ss::KArgs k = base_args(b, ss::MODE_STEP);
-    k.actions = ss_batch::R(actions); k.task_rand = ss_batch::R(task_rand); k.obs = ss_batch::R(obs); k.reward = ss_batch::R(reward);
-    k.terminated = term; k.truncated = trunc;
+    ss::KArgs k = step_args(b, actions, task_rand, obs, reward, term, trunc);
     k.fused_reset = 1; k.obs2 = ss_batch::R(obs_next); k.task_rand2 = ss_batch::R(reset_task_rand);
     if (b->cfg.state_init == SS_INIT_FALL) k.fall_actions = ss_batch::R(b->fall_actions);
     return run(b, k, stream);
@@ -294,10 +286,9 @@ struct ss_api {
     if (!b || !actions) return fail(SS_ERR_INVALID, "null argument");
     if (!b->d_im) return fail(SS_ERR_INVALID, "ss_imitation_bind first");
     if (rand && !b->im_io.sampling_cdf) return fail(SS_ERR_INVALID, "re-initialisation needs ss_imitation_io.sampling_cdf");
-    ss::KArgs k = base_args(b, ss::MODE_STEP);
-    k.actions = ss_batch::R(actions);
-    k.obs = ss_batch::R(b->im_io.obs_final); k.obs2 = ss_batch::R(b->im_io.obs_next); k.obs_stride = b->im_io.obs_stride;
-    k.im = b->d_im; k.im_rand = rand;                        // reward / flags come from the imitation part
+    ss::KArgs k = step_args(b, actions, nullptr, b->im_io.obs_final, nullptr, nullptr, nullptr);
+    k.obs2 = ss_batch::R(b->im_io.obs_next); k.obs_stride = b->im_io.obs_stride;
+    k.im = b->d_im; k.im_rand = rand;
     return run(b, k, stream);
   }
   // ---- state by field (device-to-device copies between the bound buffers and the caller's)
@@ -308,15 +299,13 @@ struct ss_api {
     const size_t N = (size_t)b->st.num_envs;
     if (!BE::set_device(b->m->device)) return fail(SS_ERR_HIP, "cannot select device");
     auto copy = [&](void *mine, size_t bytes) { return (set ? BE::copy_d2d(mine, buf, bytes, stream) : BE::copy_d2d(buf, mine, bytes, stream)) ? SS_OK : fail(SS_ERR_HIP, "device copy failed"); };
+    auto copy2 = [&](void *mine, void *prev, size_t bytes) {   // a set also overwrites the state of the last forward pass
+      if (int rc = copy(mine, bytes)) return rc;
+      return set ? copy(prev, bytes) : SS_OK;
+    };
     switch (field) {
-      case SS_FIELD_QPOS: {
-        if (int rc = copy(b->st.qpos, N * h.nq * 4)) return rc;
-        return set ? (BE::copy_d2d(b->st.qpos_prev, buf, N * h.nq * 4, stream) ? SS_OK : fail(SS_ERR_HIP, "device copy failed")) : SS_OK;
-      }
-      case SS_FIELD_QVEL: {
-        if (int rc = copy(b->st.qvel, N * h.nv * 4)) return rc;
-        return set ? (BE::copy_d2d(b->st.qvel_prev, buf, N * h.nv * 4, stream) ? SS_OK : fail(SS_ERR_HIP, "device copy failed")) : SS_OK;
-      }
+      case SS_FIELD_QPOS: return copy2(b->st.qpos, b->st.qpos_prev, N * h.nq * 4);
+      case SS_FIELD_QVEL: return copy2(b->st.qvel, b->st.qvel_prev, N * h.nv * 4);
       case SS_FIELD_QACC_WARM: return copy(b->st.qacc_warm, N * h.nv * 4);
       case SS_FIELD_CUR_T: return copy(b->st.cur_t, N * 4);
       default: break;
@@ -353,115 +342,122 @@ struct ss_api {
     k.actions = ss_batch::R(torques); k.out0 = ss_batch::R(M); k.out1 = ss_batch::R(bias); k.out2 = ss_batch::R(qacc);
     return run(b, k, stream);
   }
+  // ---- the small entries: queries, the setters of caller-owned buffers, teardown
+  static int model_create_from_mjcf(const char *xml, size_t len, const ss_mjcf_options *opt, int device, ss_model **out) {
+    if (!xml || !out) return fail(SS_ERR_INVALID, "null argument");
+    ss::mjcf::Compiled c; std::string e;
+    if (!ss::mjcf::compile(xml, len ? len : std::strlen(xml), opt, c, e)) return fail(SS_ERR_INVALID, "MJCF: " + e);
+    return model_create(&c.desc, device, out);
+  }
+  static int model_dims(const ss_model *m, int32_t *nq, int32_t *nv, int32_t *nu, int32_t *nb) {
+    if (!m) return fail(SS_ERR_INVALID, "null model");
+    if (nq) *nq = m->hm.h.nq;
+    if (nv) *nv = m->hm.h.nv;
+    if (nu) *nu = m->hm.h.nu;
+    if (nb) *nb = m->hm.h.nb;
+    return SS_OK;
+  }
+  static int model_elimination_tree(const ss_model *m, int32_t *root, int32_t *levels, int32_t *widest, int32_t *widths, int32_t *most_children) {
+    if (!m) return fail(SS_ERR_INVALID, "null model");
+    const ss::HdrC &c = m->hm.hc;
+    if (root) *root = c.root;
+    if (levels) *levels = c.nlev;
+    if (widest) *widest = m->hm.h.maxlev;
+    if (widths) {
+      widths[0] = c.pel_level;
+      for (int L = 1; L <= c.nlev && L <= 32; L++) widths[L] = (int)((c.nkpack[(L - 1) >> 4] >> (4 * ((L - 1) & 15))) & 15ull) + 1;
+    }
+    if (most_children) most_children[0] = (int)((c.chain & 0xffffull) | ((c.neg & 0x7fffull) << 16));
+    if (most_children) for (int L = 1; L <= c.nlev && L <= 32; L++) most_children[L] = (L <= 21 && c.cpack != ~0ull) ? (int)((c.cpack >> (3 * (L - 1))) & 7ull) : -1;
+    return SS_OK;
+  }
+  static void batch_destroy(ss_batch *b) {
+    if (!b) return;
+    BE::free_(b->d_kin); BE::free_(b->d_im); BE::free_(b->d_counter); BE::free_(b->d_prof); BE::free_(b->d_sched);   // (null where never allocated)
+    delete b;
+  }
+  template <class T> static int set(ss_batch *b, T ss_batch::*member, T value) {   // a caller-owned buffer (or null: off again)
+    if (!b) return fail(SS_ERR_INVALID, "null batch");
+    b->*member = value;
+    return SS_OK;
+  }
+  static int set_launch_geometry(ss_batch *b, int32_t envs_per_wg, int32_t max_workgroups) {
+    if (!b || envs_per_wg < 0 || envs_per_wg > b->envs_per_wg || max_workgroups < 0)
+      return fail(SS_ERR_INVALID, "envs per workgroup must be in [0, ss_launch_info's value], max_workgroups >= 0");
+    b->fixed_envs_per_wg = envs_per_wg; b->max_wgs = max_workgroups;
+    return SS_OK;
+  }
+  static int set_body_outputs(ss_batch *b, float *xpos, float *xmat) {
+    if (!b || (!xpos) != (!xmat)) return fail(SS_ERR_INVALID, "pass both buffers or neither");
+    b->body_xpos = xpos; b->body_xmat = xmat;
+    return SS_OK;
+  }
+  static int schedule_longest_first(ss_batch *b, void *stream) {
+    if (!b) return fail(SS_ERR_INVALID, "null batch");
+    if (!BE::set_device(b->m->device)) return fail(SS_ERR_HIP, "cannot select device");
+    if (!b->d_sched) b->d_sched = (int32_t *)BE::alloc(2 * sizeof(int32_t) * (size_t)b->st.num_envs);
+    if (!b->d_sched) return fail(SS_ERR_NOMEM, "device allocation failed");
+    const char *err = BE::order_by_key(b->st, b->m->hm.h.nv, b->d_sched + b->st.num_envs, b->d_sched, stream);
+    if (err) return fail(SS_ERR_HIP, err);
+    b->order = b->d_sched;
+    return SS_OK;
+  }
+  static int gae(const float *rew, const float *nd, const float *ndead, const float *val, const float *boot, int32_t T, int32_t N,
+                 float gamma, float tau, float *adv, float *ret, void *stream) {
+    if (!rew || !nd || !ndead || !val || !adv || !ret) return fail(SS_ERR_INVALID, "null argument");
+    if (T < 1 || N < 1) return fail(SS_ERR_INVALID, "T and N must be positive");
+    const char *err = BE::gae(rew, nd, ndead, val, boot, T, N, gamma, tau, adv, ret, stream);
+    return err ? fail(SS_ERR_HIP, err) : SS_OK;
+  }
+  static int debug_prof(ss_batch *b, unsigned long long *out, int n) {
+    if (!b || !out || !b->d_prof) return fail(SS_ERR_INVALID, "not a profiling build");
+    return BE::download(out, b->d_prof, (size_t)n * 8) ? SS_OK : fail(SS_ERR_HIP, "download of the profile counters failed");
+  }
+  static int launch_info(const ss_batch *b, int32_t *epw, int32_t *lds, int32_t *regs) {
+    if (!b) return fail(SS_ERR_INVALID, "null batch");
+    if (epw) *epw = b->envs_per_wg;
+    if (lds) *lds = (int32_t)b->lds_bytes;
+    if (regs) *regs = b->kernel_regs;
+    return SS_OK;
+  }
 };
 
-// The extern "C" surface, identical for every backend.
-#define SS_DEFINE_C_API(BE)                                                                                          \
-  extern "C" {                                                                                                       \
+// The extern "C" surface of include/smplsim_hip.h for a backend.  Used once per library, by the translation unit that owns the backend
+// (smplsim_hip.hip; tests/wave_emu/emu.cpp; tests/host_paths_check.cpp).  Every entry is one line: it opens the handle's error scope
+// (ss::HandleScope) and delegates to ss_api<BE>, which checks the handle and everything else.
+#define SS_DEFINE_C_API(BE) \
+  extern "C" { \
   int ss_model_create(const ss_model_desc *d, int dev, ss_model **out) { return ss_api<BE>::model_create(d, dev, out); } \
   int ss_model_create_shapes(const ss_model_desc *d, int32_t n, int dev, ss_model **out) { return ss_api<BE>::model_create_shapes(d, n, dev, out); } \
-  void ss_model_destroy(ss_model *m) { ss_api<BE>::model_destroy(m); }                                               \
-  int ss_model_dims(const ss_model *m, int32_t *nq, int32_t *nv, int32_t *nu, int32_t *nb) {                          \
-    ss::HandleScope hs_(m ? &m->err : nullptr);                                                                      \
-    if (!m) return ss_api<BE>::fail(SS_ERR_INVALID, "null model");                                                   \
-    if (nq) *nq = m->hm.h.nq;                                                                                        \
-    if (nv) *nv = m->hm.h.nv;                                                                                        \
-    if (nu) *nu = m->hm.h.nu;                                                                                        \
-    if (nb) *nb = m->hm.h.nb;                                                                                        \
-    return SS_OK;                                                                                                    \
-  }                                                                                                                  \
-  int ss_model_elimination_tree(const ss_model *m, int32_t *root, int32_t *levels, int32_t *widest, int32_t *widths, int32_t *most_children) { \
-    ss::HandleScope hs_(m ? &m->err : nullptr);                                                                      \
-    if (!m) return ss_api<BE>::fail(SS_ERR_INVALID, "null model");                                                   \
-    const ss::HdrC &c = m->hm.hc;                                                                                    \
-    if (root) *root = c.root;                                                                                        \
-    if (levels) *levels = c.nlev;                                                                                    \
-    if (widest) *widest = m->hm.h.maxlev;                                                                            \
-    if (widths) {                                                                                                    \
-      widths[0] = c.pel_level;                                                                                       \
-      for (int L = 1; L <= c.nlev && L <= 32; L++) widths[L] = (int)((c.nkpack[(L - 1) >> 4] >> (4 * ((L - 1) & 15))) & 15ull) + 1; \
-    }                                                                                                                \
-    if (most_children) most_children[0] = (int)((c.chain & 0xffffull) | ((c.neg & 0x7fffull) << 16));                                            \
-    if (most_children) for (int L = 1; L <= c.nlev && L <= 32; L++) most_children[L] = (L <= 21 && c.cpack != ~0ull) ? (int)((c.cpack >> (3 * (L - 1))) & 7ull) : -1; \
-    return SS_OK;                                                                                                    \
-  }                                                                                                                  \
+  int ss_model_create_from_mjcf(const char *xml, size_t len, const ss_mjcf_options *opt, int dev, ss_model **out) { return ss_api<BE>::model_create_from_mjcf(xml, len, opt, dev, out); } \
+  void ss_model_destroy(ss_model *m) { ss_api<BE>::model_destroy(m); } \
+  int ss_model_dims(const ss_model *m, int32_t *nq, int32_t *nv, int32_t *nu, int32_t *nb) { ss::HandleScope hs(m); return ss_api<BE>::model_dims(m, nq, nv, nu, nb); } \
+  int ss_model_elimination_tree(const ss_model *m, int32_t *root, int32_t *levels, int32_t *widest, int32_t *widths, int32_t *most_children) { ss::HandleScope hs(m); return ss_api<BE>::model_elimination_tree(m, root, levels, widest, widths, most_children); } \
   int ss_obs_size(const ss_model *m, const ss_env_cfg *c) { return (m && c) ? ss::obs_size(m->hm.h, *c) : SS_ERR_INVALID; } \
-  int ss_batch_create(const ss_model *m, const ss_env_cfg *c, const ss_state *s, ss_batch **o) { ss::HandleScope hs_(m ? &m->err : nullptr); return ss_api<BE>::batch_create(m, c, s, o); } \
-  void ss_batch_destroy(ss_batch *b) { if (b) { BE::free_(b->d_kin); BE::free_(b->d_im); BE::free_(b->d_counter); BE::free_(b->d_prof); BE::free_(b->d_sched); delete b; } }          \
-  int ss_set_order(ss_batch *b, const int32_t *order) { ss::HandleScope hs_(b ? &b->err : nullptr);                                                              \
-    if (!b) return ss_api<BE>::fail(SS_ERR_INVALID, "null batch");                                                  \
-    b->order = order; return SS_OK;                                                                                  \
-  }                                                                                                                  \
-  int ss_set_launch_geometry(ss_batch *b, int32_t envs_per_wg, int32_t max_workgroups) { ss::HandleScope hs_(b ? &b->err : nullptr);                              \
-    if (!b || envs_per_wg < 0 || envs_per_wg > b->envs_per_wg || max_workgroups < 0)                                   \
-      return ss_api<BE>::fail(SS_ERR_INVALID, "envs per workgroup must be in [0, ss_launch_info's value], max_workgroups >= 0"); \
-    b->fixed_envs_per_wg = envs_per_wg; b->max_wgs = max_workgroups; return SS_OK;                                     \
-  }                                                                                                                  \
-  int ss_set_body_outputs(ss_batch *b, float *xpos, float *xmat) { ss::HandleScope hs_(b ? &b->err : nullptr);                                                    \
-    if (!b || (!xpos) != (!xmat)) return ss_api<BE>::fail(SS_ERR_INVALID, "pass both buffers or neither");           \
-    b->body_xpos = xpos; b->body_xmat = xmat; return SS_OK;                                                          \
-  }                                                                                                                  \
-  int ss_set_power_output(ss_batch *b, float *power) { ss::HandleScope hs_(b ? &b->err : nullptr);                                                               \
-    if (!b) return ss_api<BE>::fail(SS_ERR_INVALID, "null batch");                                                  \
-    b->power = power; return SS_OK;                                                                                  \
-  }                                                                                                                  \
-  int ss_debug_self_truncation(ss_batch *b, int32_t *counts) { ss::HandleScope hs_(b ? &b->err : nullptr);                                                       \
-    if (!b) return ss_api<BE>::fail(SS_ERR_INVALID, "null batch");                                                  \
-    b->self_trunc = counts; return SS_OK;                                                                            \
-  }                                                                                                                  \
-  int ss_debug_self_contacts(ss_batch *b, float *records) { ss::HandleScope hs_(b ? &b->err : nullptr);                                                           \
-    if (!b) return ss_api<BE>::fail(SS_ERR_INVALID, "null batch");                                                  \
-    b->dbg_self = records; return SS_OK;                                                                             \
-  }                                                                                                                  \
-  int ss_schedule_longest_first(ss_batch *b, void *stream) { ss::HandleScope hs_(b ? &b->err : nullptr);                                                        \
-    if (!b) return ss_api<BE>::fail(SS_ERR_INVALID, "null batch");                                                  \
-    if (!BE::set_device(b->m->device)) return ss_api<BE>::fail(SS_ERR_HIP, "cannot select device");                  \
-    if (!b->d_sched) b->d_sched = (int32_t *)BE::alloc(2 * sizeof(int32_t) * (size_t)b->st.num_envs);                  \
-    if (!b->d_sched) return ss_api<BE>::fail(SS_ERR_NOMEM, "device allocation failed");                              \
-    const char *err = BE::order_by_key(b->st, b->m->hm.h.nv, b->d_sched + b->st.num_envs, b->d_sched, stream);         \
-    if (err) return ss_api<BE>::fail(SS_ERR_HIP, err);                                                               \
-    b->order = b->d_sched; return SS_OK;                                                                             \
-  }                                                                                                                  \
-  int ss_gae(const float *rew, const float *nd, const float *ndead, const float *val, const float *boot, int32_t T,   \
-             int32_t N, float gamma, float tau, float *adv, float *ret, void *stream) {                             \
-    if (!rew || !nd || !ndead || !val || !adv || !ret) return ss_api<BE>::fail(SS_ERR_INVALID, "null argument");     \
-    if (T < 1 || N < 1) return ss_api<BE>::fail(SS_ERR_INVALID, "T and N must be positive");                         \
-    const char *err = BE::gae(rew, nd, ndead, val, boot, T, N, gamma, tau, adv, ret, stream);                         \
-    return err ? ss_api<BE>::fail(SS_ERR_HIP, err) : SS_OK;                                                          \
-  }                                                                                                                  \
-  int ss_debug_prof(ss_batch *b, unsigned long long *out, int n) { ss::HandleScope hs_(b ? &b->err : nullptr);                                                   \
-    if (!b || !out || !b->d_prof) return ss_api<BE>::fail(SS_ERR_INVALID, "not a profiling build");                 \
-    return BE::download(out, b->d_prof, (size_t)n * 8) ? SS_OK : SS_ERR_HIP;                                         \
-  }                                                                   \
-  int ss_reset(ss_batch *b, const uint8_t *mask, const float *fa, const float *tr, float *obs, void *st) { ss::HandleScope hs_(b ? &b->err : nullptr); return ss_api<BE>::reset(b, mask, fa, tr, obs, st); } \
-  int ss_step(ss_batch *b, const float *a, const float *tr, float *obs, float *rew, uint8_t *te, uint8_t *tu, void *st) { ss::HandleScope hs_(b ? &b->err : nullptr); return ss_api<BE>::step(b, a, tr, obs, rew, te, tu, st); } \
-  int ss_step_autoreset(ss_batch *b, const float *a, const float *tr, const float *tr2, float *obs, float *obs_next, float *rew, \
-                        uint8_t *te, uint8_t *tu, void *st) { ss::HandleScope hs_(b ? &b->err : nullptr); return ss_api<BE>::step_autoreset(b, a, tr, tr2, obs, obs_next, rew, te, tu, st); } \
-  int ss_set_fall_actions(ss_batch *b, const float *fa) {                                                             \
-    if (!b) return ss_api<BE>::fail(SS_ERR_INVALID, "null batch");                                                  \
-    b->fall_actions = fa; return SS_OK;                                                                              \
-  }                                                                                                                  \
-  int ss_get_state(ss_batch *b, int32_t field, void *buf, void *st) { ss::HandleScope hs_(b ? &b->err : nullptr); return ss_api<BE>::state_field(b, field, buf, false, st); } \
-  int ss_set_state(ss_batch *b, int32_t field, const void *buf, void *st) { ss::HandleScope hs_(b ? &b->err : nullptr); return ss_api<BE>::state_field(b, field, const_cast<void *>(buf), true, st); } \
-  int ss_imitation_bind(ss_batch *b, const ss_imitation_io *io) { ss::HandleScope hs_(b ? &b->err : nullptr); return ss_api<BE>::imitation_bind(b, io); } \
-  int ss_imitation_step_fused(ss_batch *b, const float *a, const float *rand, void *st) { ss::HandleScope hs_(b ? &b->err : nullptr); return ss_api<BE>::imitation_step_fused(b, a, rand, st); } \
-  int ss_substep(ss_batch *b, const float *a, int n, void *st) { ss::HandleScope hs_(b ? &b->err : nullptr); return ss_api<BE>::substep(b, a, n, st); }          \
-  int ss_kinematics(ss_batch *b, float *xpos, float *xmat, void *st) { ss::HandleScope hs_(b ? &b->err : nullptr); return ss_api<BE>::kinematics(b, xpos, xmat, st); } \
-  int ss_debug_forward(ss_batch *b, const float *tq, float *M, float *bias, float *qacc, void *st) { ss::HandleScope hs_(b ? &b->err : nullptr); return ss_api<BE>::debug_forward(b, tq, M, bias, qacc, st); } \
-  int ss_launch_info(const ss_batch *b, int32_t *epw, int32_t *lds, int32_t *regs) { ss::HandleScope hs_(b ? &b->err : nullptr);                                 \
-    if (!b) return ss_api<BE>::fail(SS_ERR_INVALID, "null batch");                                                   \
-    if (epw) *epw = b->envs_per_wg;                                                                                  \
-    if (lds) *lds = (int32_t)b->lds_bytes;                                                                           \
-    if (regs) *regs = b->kernel_regs;                                                                                \
-    return SS_OK;                                                                                                    \
-  }                                                                                                                  \
-  const char *ss_last_error(void) { return ss::last_error().c_str(); }                                               \
-  const char *ss_model_last_error(const ss_model *m) { return m ? m->err.c_str() : ""; }                               \
-  const char *ss_batch_last_error(const ss_batch *b) { return b ? b->err.c_str() : ""; }                               \
-  int ss_model_create_from_mjcf(const char *xml, size_t len, const ss_mjcf_options *opt, int dev, ss_model **out) {   \
-    if (!xml || !out) return ss_api<BE>::fail(SS_ERR_INVALID, "null argument");                                      \
-    ss::mjcf::Compiled c; std::string e;                                                                             \
-    if (!ss::mjcf::compile(xml, len ? len : std::strlen(xml), opt, c, e)) return ss_api<BE>::fail(SS_ERR_INVALID, "MJCF: " + e); \
-    return ss_api<BE>::model_create(&c.desc, dev, out);                                                              \
-  }                                                                                                                  \
+  int ss_batch_create(const ss_model *m, const ss_env_cfg *c, const ss_state *s, ss_batch **o) { ss::HandleScope hs(m); return ss_api<BE>::batch_create(m, c, s, o); } \
+  void ss_batch_destroy(ss_batch *b) { ss_api<BE>::batch_destroy(b); } \
+  int ss_set_order(ss_batch *b, const int32_t *order) { ss::HandleScope hs(b); return ss_api<BE>::set(b, &ss_batch::order, order); } \
+  int ss_set_power_output(ss_batch *b, float *power) { ss::HandleScope hs(b); return ss_api<BE>::set(b, &ss_batch::power, power); } \
+  int ss_set_fall_actions(ss_batch *b, const float *fa) { ss::HandleScope hs(b); return ss_api<BE>::set(b, &ss_batch::fall_actions, fa); } \
+  int ss_debug_self_truncation(ss_batch *b, int32_t *counts) { ss::HandleScope hs(b); return ss_api<BE>::set(b, &ss_batch::self_trunc, counts); } \
+  int ss_debug_self_contacts(ss_batch *b, float *records) { ss::HandleScope hs(b); return ss_api<BE>::set(b, &ss_batch::dbg_self, records); } \
+  int ss_set_launch_geometry(ss_batch *b, int32_t envs_per_wg, int32_t max_workgroups) { ss::HandleScope hs(b); return ss_api<BE>::set_launch_geometry(b, envs_per_wg, max_workgroups); } \
+  int ss_set_body_outputs(ss_batch *b, float *xpos, float *xmat) { ss::HandleScope hs(b); return ss_api<BE>::set_body_outputs(b, xpos, xmat); } \
+  int ss_schedule_longest_first(ss_batch *b, void *stream) { ss::HandleScope hs(b); return ss_api<BE>::schedule_longest_first(b, stream); } \
+  int ss_launch_info(const ss_batch *b, int32_t *epw, int32_t *lds, int32_t *regs) { ss::HandleScope hs(b); return ss_api<BE>::launch_info(b, epw, lds, regs); } \
+  int ss_debug_prof(ss_batch *b, unsigned long long *out, int n) { ss::HandleScope hs(b); return ss_api<BE>::debug_prof(b, out, n); } \
+  int ss_reset(ss_batch *b, const uint8_t *mask, const float *fa, const float *tr, float *obs, void *st) { ss::HandleScope hs(b); return ss_api<BE>::reset(b, mask, fa, tr, obs, st); } \
+  int ss_step(ss_batch *b, const float *a, const float *tr, float *obs, float *rew, uint8_t *te, uint8_t *tu, void *st) { ss::HandleScope hs(b); return ss_api<BE>::step(b, a, tr, obs, rew, te, tu, st); } \
+  int ss_step_autoreset(ss_batch *b, const float *a, const float *tr, const float *tr2, float *obs, float *obs_next, float *rew, uint8_t *te, uint8_t *tu, void *st) { ss::HandleScope hs(b); return ss_api<BE>::step_autoreset(b, a, tr, tr2, obs, obs_next, rew, te, tu, st); } \
+  int ss_get_state(ss_batch *b, int32_t field, void *buf, void *st) { ss::HandleScope hs(b); return ss_api<BE>::state_field(b, field, buf, false, st); } \
+  int ss_set_state(ss_batch *b, int32_t field, const void *buf, void *st) { ss::HandleScope hs(b); return ss_api<BE>::state_field(b, field, const_cast<void *>(buf), true, st); } \
+  int ss_imitation_bind(ss_batch *b, const ss_imitation_io *io) { ss::HandleScope hs(b); return ss_api<BE>::imitation_bind(b, io); } \
+  int ss_imitation_step_fused(ss_batch *b, const float *a, const float *rand, void *st) { ss::HandleScope hs(b); return ss_api<BE>::imitation_step_fused(b, a, rand, st); } \
+  int ss_substep(ss_batch *b, const float *a, int n, void *st) { ss::HandleScope hs(b); return ss_api<BE>::substep(b, a, n, st); } \
+  int ss_kinematics(ss_batch *b, float *xpos, float *xmat, void *st) { ss::HandleScope hs(b); return ss_api<BE>::kinematics(b, xpos, xmat, st); } \
+  int ss_debug_forward(ss_batch *b, const float *tq, float *M, float *bias, float *qacc, void *st) { ss::HandleScope hs(b); return ss_api<BE>::debug_forward(b, tq, M, bias, qacc, st); } \
+  int ss_gae(const float *rew, const float *nd, const float *ndead, const float *val, const float *boot, int32_t T, int32_t N, float gamma, float tau, float *adv, float *ret, void *stream) { return ss_api<BE>::gae(rew, nd, ndead, val, boot, T, N, gamma, tau, adv, ret, stream); } \
+  const char *ss_last_error(void) { return ss::last_error().c_str(); } \
+  const char *ss_model_last_error(const ss_model *m) { return m ? m->err.c_str() : ""; } \
+  const char *ss_batch_last_error(const ss_batch *b) { return b ? b->err.c_str() : ""; } \
   }

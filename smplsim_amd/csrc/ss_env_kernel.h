@@ -1,5 +1,5 @@
 // ss_env_kernel.h — the gfx950 step kernel template, shared by the translation units that instantiate it (smplsim_hip.hip: the
-// plain / body-output / shaped flavours and the C ABI; smplsim_hip_sc.hip: body-body contacts; smplsim_hip_im.hip: the imitation
+// plain / body-output / shaped instantiations and the C ABI; smplsim_hip_sc.hip: body-body contacts; smplsim_hip_im.hip: the imitation
 // step).  Three units so that they compile side by side: every instantiation of the state machine costs ~15-25 s of hipcc.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,11 +24,11 @@
 
 namespace ss {
 typedef void (*kern_t)(const KArgs);
-// instantiations that live in the other translation units (nullptr = not compiled for this size class)
-kern_t pick_kernel_selfcol(int variant, bool shaped, bool imit, const Hdr &h, const HdrC &hc);
-kern_t pick_kernel_imitation(int variant, bool shaped, const Hdr &h, const HdrC &hc);
-kern_t pick_kernel_imitation_selfcol(int variant, bool shaped, const Hdr &h, const HdrC &hc);
-kern_t pick_kernel_x(int flavour, const Hdr &h, const HdrC &hc);                      // smplsim_hip_x.hip: the SMPL-X/H size class
+// instantiations that live in the other translation units, by KernelKey (ss_hdr.h); nullptr = no such instantiation
+kern_t pick_kernel_selfcol(const KernelKey &key, const Hdr &h, const HdrC &hc);             // smplsim_hip_sc.hip: body-body contacts
+kern_t pick_kernel_imitation(const KernelKey &key, const Hdr &h, const HdrC &hc);           // smplsim_hip_im.hip: the imitation step
+kern_t pick_kernel_imitation_selfcol(const KernelKey &key, const Hdr &h, const HdrC &hc);   // smplsim_hip_im.hip: both
+kern_t pick_kernel_x(const KernelKey &key, const Hdr &h, const HdrC &hc);                   // smplsim_hip_x.hip: the SMPL-X/H size class without either
 }  // namespace ss
 
 namespace {

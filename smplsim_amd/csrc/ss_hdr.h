@@ -344,4 +344,30 @@ inline size_t launch_lds_bytes(const KArgs &k, int e) {
   return (size_t)((k.h.shared_words + 3) & ~3) * 4 + ((size_t)e * env_slice_floats(k) + (k.cfg.self_collision ? ss_pool_floats(k.sc) : 0)) * sizeof(real);
 }
 
+// Which instantiation of the step kernel a launch runs: the size class (kernel_variant) and the template switches.  bodyout is the
+// kernel's BODYOUT, not the caller's wish alone: only the plain kernel exists without the body-frame outputs.
+struct KernelKey { int variant; bool bodyout, shaped, selfcol, imit; };
+inline KernelKey kernel_key(const KArgs &k) {
+  KernelKey key{kernel_variant(k.h), false, k.st.shape_id != nullptr, k.cfg.self_collision != 0, k.im != nullptr};
+  const bool wanted = (k.out0 || k.power) && (k.mode == MODE_STEP || k.mode == MODE_RESET);
+  key.bodyout = wanted || key.shaped || key.selfcol || key.imit;
+  return key;
+}
+
+// Grid of a step launch.  envs_per_wg is what fits a CU (the batch's); fixed_epw / max_wgs > 0 are the caller's (ss_set_launch_geometry).
+// A launch needs lds_fixed + envs per workgroup * lds_per_env bytes of LDS (launch_lds_bytes).
+struct LaunchGeometry { int wgs, envs_per_wg; size_t lds_bytes; };
+inline LaunchGeometry launch_geometry(int nenv, int cus, int envs_per_wg, int fixed_epw, int max_wgs, size_t lds_capacity, size_t lds_fixed, size_t lds_per_env) {
+  // small batches: spread the envs over all CUs instead of filling a third of them with full workgroups — a wave that
+  // shares its CU with 3 others runs ~13% faster than one of 12 (1024 envs: 1.27 -> 1.13 ms per step launch)
+  const int per_cu = (nenv + cus - 1) / cus;
+  if (fixed_epw > 0) envs_per_wg = fixed_epw;
+  else if (per_cu < envs_per_wg) envs_per_wg = per_cu < 1 ? 1 : per_cu;
+  LaunchGeometry g{(nenv + envs_per_wg - 1) / envs_per_wg, envs_per_wg, lds_fixed + (size_t)envs_per_wg * lds_per_env};
+  const int resident = cus * (int)(lds_capacity / g.lds_bytes > 0 ? lds_capacity / g.lds_bytes : 1);
+  if (g.wgs > resident) g.wgs = resident;                    // persistent: one resident set of workgroups
+  if (max_wgs > 0 && g.wgs > max_wgs) g.wgs = max_wgs;       // the caller shares the GPU between concurrent batches
+  return g;
+}
+
 }  // namespace ss

@@ -230,6 +230,7 @@ void lane_entry(int lane, void *arg) {
   LaunchCtx *c = (LaunchCtx *)arg;
   WaveEmu w{c->m, lane};
   int mode = c->k->mode;
+  // ss_env_kernel's driver, spelt out twice on purpose: shared as one force-inlined function it changed the device code (smplsim_hip.hip 86 969 -> 86 181 lines of assembly, other spills in smplsim_hip_im.hip)
 #ifndef SS_F64
   if (c->k->im) {                                            // the IMIT instantiation of the GPU kernel (smplsim_hip.hip)
     const ss::mo::ImFused *f = static_cast<const ss::mo::ImFused *>(c->k->im);
@@ -249,6 +250,24 @@ void lane_entry(int lane, void *arg) {
     if (!again) break;
     mode = ss::MODE_RESET;
   }
+}
+
+// The emulator's choice of instantiation, by the key the GPU library uses (ss_hdr.h).  It always instantiates BODYOUT = true (the
+// outputs are null-checked at run time), so key.bodyout takes no part, and imitation is a run-time branch of lane_entry.
+typedef void (*entry_t)(int, void *);
+entry_t pick_entry(const ss::KernelKey &key, const ss::Hdr &h, const ss::HdrC &hc) {
+  if (key.variant != 0 && key.variant != 1) return nullptr;
+  if (key.imit && key.selfcol && (key.shaped || key.variant != 0)) return nullptr;   // as on the GPU: no such instantiation
+  if (key.selfcol) {
+    if (key.variant == 0) return key.shaped ? lane_entry<2, 2, 1, 1, true, ss::HdrRuntime, true> : lane_entry<2, 2, 1, 1, false, ss::HdrRuntime, true>;
+    return key.shaped ? lane_entry<3, 3, 2, 2, true, ss::HdrRuntime, true> : lane_entry<3, 3, 2, 2, false, ss::HdrRuntime, true>;
+  }
+  // like the GPU launcher: the packaged models without per-env shapes run the compile-time-layout instantiations
+  const bool fixed = !key.shaped && !getenv("SS_EMU_GENERIC");
+  if (key.variant == 0 && fixed && ss::HdrSmplFixed::matches(h, hc)) return lane_entry<2, 2, 1, 1, false, ss::HdrSmplFixed>;
+  if (key.variant == 0) return key.shaped ? lane_entry<2, 2, 1, 1, true> : lane_entry<2, 2, 1, 1, false>;
+  if (fixed && ss::HdrSmplxFixed::matches(h, hc)) return lane_entry<3, 3, 2, 2, false, ss::HdrSmplxFixed>;
+  return key.shaped ? lane_entry<3, 3, 2, 2, true> : lane_entry<3, 3, 2, 2, false>;
 }
 
 struct EmuBackend {
@@ -330,8 +349,9 @@ struct EmuBackend {
     for (int wv = 0; wv * per < a.N; wv++) { ImCtx c{&a, wv, machine()}; run_wave(machine(), lpe == 32 ? im_entry<32> : im_entry<64>, &c); }
     return nullptr;
   }
-  static const char *launch(const ss::KArgs &k, int nenv, int envs_per_wg, size_t lds_bytes, void *, int, int) {
-    (void)envs_per_wg; (void)lds_bytes;
+  static const char *launch(const ss::KArgs &k, int nenv, int, size_t, void *, int, int) {   // one wavefront at a time: no launch geometry
+    entry_t entry = pick_entry(ss::kernel_key(k), k.h, k.hc);
+    if (!entry) return "no kernel variant for this model size";
     static thread_local Machine *m = new Machine();
     std::vector<ss::real> L(ss::env_slice_floats(k));
     // the workgroup's shared dense block (lock word first); NaNs behind it: a read past the block's end shows up in the results instead of going unnoticed
@@ -354,21 +374,6 @@ struct EmuBackend {
         }
       }
       LaunchCtx c{&k, k.shared_g, L.data(), k.order ? k.order[env] : env, m, pool.data()};
-      void (*entry)(int, void *) = nullptr;
-      const int variant = ss::kernel_variant(k.h);
-      if (k.cfg.self_collision) {
-        if (variant == 0) entry = k.st.shape_id ? lane_entry<2, 2, 1, 1, true, ss::HdrRuntime, true> : lane_entry<2, 2, 1, 1, false, ss::HdrRuntime, true>;
-        else if (variant == 1) entry = k.st.shape_id ? lane_entry<3, 3, 2, 2, true, ss::HdrRuntime, true> : lane_entry<3, 3, 2, 2, false, ss::HdrRuntime, true>;
-        else return "no kernel variant for this model size";
-        run_wave(m, entry, &c);
-        continue;
-      }
-      // like the GPU launcher: the SMPL-sized model without per-env shapes runs the compile-time-layout instantiation
-      if (variant == 0 && !k.st.shape_id && ss::HdrSmplFixed::matches(k.h, k.hc) && !getenv("SS_EMU_GENERIC")) entry = lane_entry<2, 2, 1, 1, false, ss::HdrSmplFixed>;
-      else if (variant == 0) entry = k.st.shape_id ? lane_entry<2, 2, 1, 1, true> : lane_entry<2, 2, 1, 1, false>;
-      else if (variant == 1 && !k.st.shape_id && ss::HdrSmplxFixed::matches(k.h, k.hc) && !getenv("SS_EMU_GENERIC")) entry = lane_entry<3, 3, 2, 2, false, ss::HdrSmplxFixed>;
-      else if (variant == 1) entry = k.st.shape_id ? lane_entry<3, 3, 2, 2, true> : lane_entry<3, 3, 2, 2, false>;
-      else return "no kernel variant for this model size";
       run_wave(m, entry, &c);
     }
     return nullptr;
@@ -390,6 +395,12 @@ extern "C" int ss_emu_narrow_phase(int kind, const double *in, double *out) {
   out[0] = n;
   for (int i = 0; i < n; i++) for (int k = 0; k < 7; k++) out[1 + 7 * i + k] = c[sc::kConOut * i + k];
   return n;
+}
+
+// test hook: the grid of a step launch (ss::launch_geometry, what HipBackend::launch calls): out = workgroups, envs per workgroup, LDS bytes
+extern "C" void ss_emu_launch_geometry(int nenv, int cus, int envs_per_wg, int fixed_epw, int max_wgs, long lds_capacity, long lds_fixed, long lds_per_env, long *out) {
+  const ss::LaunchGeometry g = ss::launch_geometry(nenv, cus, envs_per_wg, fixed_epw, max_wgs, (size_t)lds_capacity, (size_t)lds_fixed, (size_t)lds_per_env);
+  out[0] = g.wgs; out[1] = g.envs_per_wg; out[2] = (long)g.lds_bytes;
 }
 
 SS_DEFINE_C_API(EmuBackend)
