@@ -64,12 +64,6 @@ struct ss_batch {
   ss_imitation_io im_io{};
 };
 
-inline bool same_pair_ids(const std::vector<int32_t> &a, const std::vector<int32_t> &b) {
-  if (a.size() != b.size()) return false;
-  for (size_t i = 0; i < a.size(); i += 2) if (a[i] != b[i]) return false;
-  return true;
-}
-
 template <class BE>
 struct ss_api {
   static int fail(int code, const std::string &msg) {
@@ -80,10 +74,7 @@ struct ss_api {
 
   static int model_create(const ss_model_desc *d, int device, ss_model **out) {
     if (!d || !out) return fail(SS_ERR_INVALID, "null argument");
-    ss_model *m = new (std::nothrow) ss_model();
-    if (!m) return fail(SS_ERR_NOMEM, "out of host memory");
-    if (!ss::build_host_model(*d, m->hm)) { std::string e = m->hm.error; delete m; return fail(SS_ERR_INVALID, e); }
-    return upload_model(m, device, m->hm.bodyc, m->hm.candc, m->hm.pairs, m->hm.geomc, out);
+    return model_create_shapes(d, 1, device, out);
   }
   template <class T> static bool up(T *&dst, const std::vector<T> &v) {
     const size_t bytes = v.size() * sizeof(T);
@@ -91,57 +82,24 @@ struct ss_api {
     if (dst && bytes && !BE::upload(dst, v.data(), bytes)) { BE::free_(dst); dst = nullptr; }
     return dst != nullptr;
   }
-  // The one way a model gets its six device tables: the shared blob and candb from m->hm, the shape-dependent ones as given (one block
-  // per body shape), the per-body elimination-tree table of the SELFCOL kernels behind the pair table.  Hands m out, or frees it.
-  static int upload_model(ss_model *m, int device, const std::vector<ss::real> &bodyc, const std::vector<ss::real> &candc,
-                          std::vector<int32_t> pairs, const std::vector<ss::real> &geomc, ss_model **out) {
-    m->device = device;
+  // The one way a model is made: num_shapes descriptions of the same humanoid with different body shapes -> one model whose geometry tables
+  // have num_shapes entries (ss_tables.h builds them), and its six device tables.  Hands the model out, or frees it.
+  static int model_create_shapes(const ss_model_desc *d, int num_shapes, int device, ss_model **out) {
+    if (!d || !out || num_shapes < 1) return fail(SS_ERR_INVALID, "null argument or num_shapes < 1");
+    ss_model *m = new (std::nothrow) ss_model();
+    if (!m) return fail(SS_ERR_NOMEM, "out of host memory");
+    ss::HostModel &hm = m->hm;
+    const std::string refusal = ss::build_host_model(d, num_shapes, getenv("SS_NO_ALIAS_LAYOUT") != nullptr, hm);
+    if (!refusal.empty()) { delete m; return fail(SS_ERR_INVALID, refusal); }
+    if (num_shapes > 1 && 12 * hm.h_sc.nb > hm.h_sc.l_Wst - hm.h_sc.l_IA) { delete m; return fail(SS_ERR_LDS, "no room for the per-env body offsets"); }   // (the aliased layout has the 12 nb by construction)
+    m->num_shapes = num_shapes; m->device = device;
     if (!BE::set_device(device)) { delete m; return fail(SS_ERR_HIP, "cannot select device"); }
-    m->hm.sc.o_sctab = (int)pairs.size();
-    pairs.insert(pairs.end(), m->hm.sctab.begin(), m->hm.sctab.end());
-    if (!(up(m->d_shared, m->hm.shared) && up(m->d_bodyc, bodyc) && up(m->d_candc, candc) && up(m->d_candb, m->hm.candb) && up(m->d_pairs, pairs) && up(m->d_geomc, geomc))) {
+    if (!(up(m->d_shared, hm.shared) && up(m->d_bodyc, hm.bodyc) && up(m->d_candc, hm.candc) && up(m->d_candb, hm.candb) && up(m->d_pairs, hm.pairs) && up(m->d_geomc, hm.geomc))) {
       model_destroy(m);                                      // (a table that failed is null: everything allocated so far is freed once)
       return fail(SS_ERR_HIP, "device table upload failed");
     }
     *out = m;
     return SS_OK;
-  }
-  // S descriptions of the same humanoid with different body shapes -> one model whose geometry tables have S entries
-  static int model_create_shapes(const ss_model_desc *d, int num_shapes, int device, ss_model **out) {
-    if (!d || !out || num_shapes < 1) return fail(SS_ERR_INVALID, "null argument or num_shapes < 1");
-    if (num_shapes == 1) return model_create(d, device, out);
-    ss_model *m = new (std::nothrow) ss_model();
-    if (!m) return fail(SS_ERR_NOMEM, "out of host memory");
-    std::vector<ss::real> bodyc, candc, geomc;
-    std::vector<int32_t> pairs;                              // per shape: the ids are the same, the bounding-sphere reaches are not
-    for (int s = 0; s < num_shapes; s++) {
-      ss::HostModel hm;
-      if (!ss::build_host_model(d[s], hm)) { std::string e = "shape " + std::to_string(s) + ": " + hm.error; delete m; return fail(SS_ERR_INVALID, e); }
-      const ss::Hdr &h = hm.h;
-      std::vector<ss::real> iw(h.nv);
-      ss::real *sf = ss::shared_reals(hm);
-      for (int i = 0; i < h.nv; i++) { iw[i] = sf[h.o_dofc + i * ss::kDofC + 4]; sf[h.o_dofc + i * ss::kDofC + 4] = 0; }
-      for (int i = 0; i < 3 * h.nb; i++) sf[h.o_boff + i] = 0;              // the two shape-dependent parts of the shared blob
-      if (s == 0) m->hm = hm;
-      else {
-        const ss::Hdr &g = m->hm.h;
-        // everything but the geometry must agree: tree, joints, limits, gains, actuators, geom types, contact set, options
-        const bool same = h.nb == g.nb && h.nv == g.nv && h.nu == g.nu && h.ncand == g.ncand && h.nbox == g.nbox && h.nslot == g.nslot &&
-                          h.shared_words == g.shared_words && h.env_floats == g.env_floats && hm.shared == m->hm.shared &&
-                          hm.candb == m->hm.candb && same_pair_ids(hm.pairs, m->hm.pairs) && hm.illegal_mask == m->hm.illegal_mask && h.dt == g.dt && h.grav == g.grav &&
-                          h.margin == g.margin && h.mu == g.mu && h.K == g.K && h.B == g.B;
-        if (!same) { delete m; return fail(SS_ERR_INVALID, "shape " + std::to_string(s) + " differs from shape 0 in more than its geometry"); }
-      }
-      bodyc.insert(bodyc.end(), hm.bodyc.begin(), hm.bodyc.end());
-      iw.resize((h.nv + 3) & ~3, ss::real(0));
-      bodyc.insert(bodyc.end(), iw.begin(), iw.end());        // block = body constants, then the dof inverse weights
-      candc.insert(candc.end(), hm.candc.begin(), hm.candc.end());
-      geomc.insert(geomc.end(), hm.geomc.begin(), hm.geomc.end());   // pair functions (self_collision batches): geoms of this shape
-      pairs.insert(pairs.end(), hm.pairs.begin(), hm.pairs.end());
-    }
-    if (12 * m->hm.h_sc.nb > m->hm.h_sc.l_Wst - m->hm.h_sc.l_IA) { delete m; return fail(SS_ERR_LDS, "no room for the per-env body offsets"); }   // (the aliased layout has the 12 nb by construction)
-    m->num_shapes = num_shapes;
-    return upload_model(m, device, bodyc, candc, std::move(pairs), geomc, out);
   }
   static void model_destroy(ss_model *m) {
     if (!m) return;

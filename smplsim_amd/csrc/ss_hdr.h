@@ -121,6 +121,14 @@ constexpr Layout make_layout(int nb, int maxlev, bool alias_w = false) {
   y.env_floats = o;
   return y;
 }
+// the host's copy of a layout into the header (every other field of g stays)
+inline void apply_layout(Hdr &g, const Layout &y) {
+  g.l_q = y.l_q; g.l_v = y.l_v; g.l_a = y.l_a; g.l_tau = y.l_tau; g.l_Fb = y.l_Fb; g.l_act = y.l_act; g.l_delta = y.l_delta; g.l_Pb = y.l_Pb; g.l_V = y.l_V;
+  g.l_diag = y.l_diag; g.l_S = y.l_S; g.l_Ab = y.l_Ab; g.l_Iown = y.l_Iown; g.l_An = y.l_An; g.l_Aown = y.l_Aown; g.ia_stride = y.ia_stride;
+  g.l_IA = y.l_IA; g.l_Gb = y.l_Gb; g.l_tmp = y.l_tmp; g.l_Ubuf = y.l_Ubuf; g.l_Wst = y.l_Wst; g.l_R = y.l_R; g.l_r = y.l_r;
+  g.a_stride = y.a_stride; g.l_Rloc = y.l_Rloc; g.l_w2 = y.l_w2;
+  g.env_floats = y.env_floats;
+}
 // can a tree use the aliased layout?  (the forward pass's scratch must fit the Aown region, the contact records must end before R)
 constexpr bool alias_layout_fits(int nb, int maxlev, int nslot) {
   const int nn = nb + 1;

@@ -10,7 +10,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -20,31 +19,41 @@
 
 namespace ss {
 
+// A model ready for upload: the headers the kernels get by value and the six device tables.
 struct HostModel {
-  Hdr h{};
-  Hdr h_sc{};                     // the same header on the plain (non-aliased) LDS layout: what body-body-contact batches run on (= h when h is not aliased)
-  std::vector<uint32_t> shared;   // tables copied into LDS once per workgroup: integer tables, then the real-valued ones
-  std::vector<real> bodyc;        // [nb][kBodyC]: off3 ipos3 mass Ibody6 invw_tr  (loaded into registers)
-  std::vector<real> candc;        // [ncand][kCandC]
-  std::vector<int32_t> candb;     // [ncand] body of each candidate, bit 8: capsule
-  std::vector<float> actc;        // [nv][4]: kp kd tlim (per dof, 0 for unactuated), [nv][2] scale offset -> in dofc
-  std::vector<int32_t> dof_act;   // [nv] actuator index of a dof or -1
-  std::vector<uint8_t> legal;     // [nb]
-  uint64_t illegal_mask = 0;      // bodies whose floor contact terminates the episode
-  int o_real = 0;                 // word offset of the real-valued part of `shared`
-  std::vector<int32_t> pairs;     // body-body candidate pairs after MuJoCo's static filters, 2 words each: b1 | b2 << 8 (normal points
-                                  // b1 -> b2), and the float bits of the pair's bounding-sphere reach r1 + r2 + margin (broad phase)
-  std::vector<real> geomc;        // [nb][kGeomC] geoms in their body frames (pair functions of the SELFCOL kernels)
-  std::vector<int32_t> sctab;     // [nb][3] elimination-tree neighbour / joint / path mask per body (SELFCOL kernels), uploaded behind the pair table
-  HdrSC sc{};
+  Hdr h{}, h_sc{};                // h_sc: the same header on the plain (non-aliased) LDS layout: what body-body-contact batches run on (= h when h is not aliased)
   HdrC hc{};                      // centred elimination tree of the plain solves
-  double meaninertia = 0;         // mjModel.stat.meaninertia (scale of the solver's termination test)
-  std::string error;
+  HdrSC sc{};
+  uint64_t illegal_mask = 0;      // bodies whose floor contact terminates the episode
+  double meaninertia = 0;         // mjModel.stat.meaninertia (scale of the solver's termination test); shape 0's
   std::string self_collision_unavailable;   // non-empty: the model cannot run with ss_env_cfg.self_collision (reason)
+  std::vector<uint32_t> shared;   // tables copied into LDS once per workgroup: integer tables, then the real-valued ones
+  std::vector<int32_t> candb;     // [ncand] body of each candidate, bit 8: capsule
+  // one block per body shape: [nb][kBodyC] off3 ipos3 mass Ibody6 invw_tr (loaded into registers; several shapes: + the dof inverse weights,
+  // shape_stride), [ncand][kCandC], [nb][kGeomC] geoms in their body frames (pair functions of the SELFCOL kernels)
+  std::vector<real> bodyc, candc, geomc;
+  std::vector<int32_t> pairs;     // body-body candidate pairs after MuJoCo's static filters, 2 words each: b1 | b2 << 8 (normal points b1 -> b2), and the float
+                                  // bits of the pair's bounding-sphere reach r1 + r2 + margin (broad phase); behind the last shape's: sc.o_sctab
 };
-
-// real-valued part of the shared blob (HostModel::shared from word h.o_real on)
-inline real *shared_reals(HostModel &m) { return reinterpret_cast<real *>(m.shared.data()); }   // index with Hdr::o_dofc / o_boff
+struct Tree {   // everything that follows from body_parent alone
+  std::vector<int> parent, chainnode, ndepth; int nlev = 0;    // node_tree
+  std::vector<int> sum_small, sum_big, sum_cover;              // subtree_sum_tables
+  HdrC hc{}; int maxlev = 1;                                   // elimination_tree (hc.o_lev: assemble_blob); maxlev = its widest level
+  std::vector<int> levrec, towards, joint, negated;            //   the level records of HdrC::o_lev; per body: neighbour towards the root (255: it is the root), joint node, S negated
+};
+// What the body shapes of one model must agree in (same_topology).  h: dims, candidate counts and physics scalars; the rest of it is filled in once per model.
+struct Topology {
+  Hdr h{};
+  Tree tree;
+  std::vector<real> dofc;         // [nv][kDofC]: arm, lo, hi, limited, invw (left 0: Shape::invw), kp, kd, tlim, ascale, aoffset, actuated, actuator index
+  std::vector<int32_t> candb, pair_ids;
+  uint64_t illegal_mask = 0;
+};
+struct Shape {   // what they may differ in
+  std::vector<real> bodyc, invw, boff, candc, geomc;           // invw [nv] dof inverse weights, boff [nb][3] body frame offsets in the parent frame (chain walk of forward_kin)
+  std::vector<int32_t> reach;                                  // float bits of the bounding-sphere reach per pair of Topology::pair_ids
+  double meaninertia = 0;
+};
 
 inline void quat2mat(const double *q, double *m) {
   double w = q[0], x = q[1], y = q[2], z = q[3];
@@ -53,6 +62,14 @@ inline void quat2mat(const double *q, double *m) {
   m[0] = 1 - 2 * (y * y + z * z); m[1] = 2 * (x * y - w * z); m[2] = 2 * (x * z + w * y);
   m[3] = 2 * (x * y + w * z); m[4] = 1 - 2 * (x * x + z * z); m[5] = 2 * (y * z - w * x);
   m[6] = 2 * (x * z - w * y); m[7] = 2 * (y * z + w * x); m[8] = 1 - 2 * (x * x + y * y);
+}
+// inertia of body b in its body frame: R diag(I) R^T, R = the inertial frame's orientation
+inline void body_frame_inertia(const ss_model_desc &d, int b, double *I) {
+  double R[9]; quat2mat(d.body_iquat + 4 * b, R);
+  for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) {
+    double s = 0; for (int k = 0; k < 3; k++) s += R[3 * i + k] * d.body_inertia[3 * b + k] * R[3 * j + k];
+    I[3 * i + j] = s;
+  }
 }
 
 // mean diagonal of the joint-space inertia matrix at qpos0 (armature included) = mjModel.stat.meaninertia.  At qpos0 every body frame of
@@ -68,11 +85,7 @@ inline double meaninertia_at_qpos0(const ss_model_desc &d) {
   for (int b = 0; b < nb; b++) {
     for (int k = 0; k < 3; k++) p[3 * b + k] = b == 0 ? d.qpos0[k] : p[3 * d.body_parent[b] + k] + d.body_pos[3 * b + k];
     for (int k = 0; k < 3; k++) c[3 * b + k] = p[3 * b + k] + d.body_ipos[3 * b + k];
-    double R[9]; quat2mat(d.body_iquat + 4 * b, R);
-    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) {
-      double s = 0; for (int k = 0; k < 3; k++) s += R[3 * i + k] * d.body_inertia[3 * b + k] * R[3 * j + k];
-      I[9 * b + 3 * i + j] = s;
-    }
+    body_frame_inertia(d, b, &I[9 * b]);
   }
   double trace = 0;
   for (int j = 0; j < nb; j++)
@@ -92,312 +105,253 @@ inline double meaninertia_at_qpos0(const ss_model_desc &d) {
   return trace / (nv > 1 ? nv : 1);
 }
 
-inline bool build_host_model(const ss_model_desc &d, HostModel &out) {
-  Hdr &h = out.h;
-  const int nb = d.nbody;
-  if (nb < 1 || nb > 63) { out.error = "nbody must be in [1,63]"; return false; }
-  if (d.body_parent[0] != -1) { out.error = "body 0 must be the root"; return false; }
-  for (int b = 1; b < nb; b++)
-    if (d.body_parent[b] < 0 || d.body_parent[b] >= b) { out.error = "parents must precede children"; return false; }
-  h.nb = nb; h.nn = nb + 1; h.nv = 6 + 3 * (nb - 1); h.nq = h.nv + 1; h.nu = d.nu;
-  // mjModel.stat.meaninertia; <= 0 (e.g. a caller of the pre-round-3 struct, zero-initialised): computed here from the description
-  out.meaninertia = d.meaninertia > 0.0 ? d.meaninertia : meaninertia_at_qpos0(d);
-  if (!(out.meaninertia > 0.0)) { out.error = "meaninertia: the inertia matrix at qpos0 has no positive diagonal"; return false; }
-  const int nn = h.nn, nv = h.nv;
-
-  // ---- node tree
-  std::vector<int> nparent(nn), ndepth(nn);
-  nparent[0] = -1; ndepth[0] = 0; nparent[1] = 0; ndepth[1] = 1;
-  for (int b = 1; b < nb; b++) {
-    int p = d.body_parent[b];
-    nparent[b + 1] = p + 1; ndepth[b + 1] = ndepth[p + 1] + 1;
-  }
-  int nlev = 0;
-  for (int n = 0; n < nn; n++) nlev = std::max(nlev, ndepth[n] + 1);
-  h.nlev = nlev;
-  const int CN = nlev;                                     // chain node table row width
-  std::vector<int> chainnode(nn * CN, 0);
-  for (int n = 0; n < nn; n++) {
-    std::vector<int> anc;                                  // root -> parent
-    for (int a = nparent[n]; a >= 0; a = nparent[a]) anc.insert(anc.begin(), a);
-    for (size_t k = 0; k < anc.size(); k++) chainnode[n * CN + k] = anc[k];
-    chainnode[n * CN + anc.size()] = n;                    // convenient: chain includes self at its depth
-  }
-  // bodies must come in depth-first order (the subtree of b is the index range [b, b + size): subtree_sum): b's parent is
+// ---- The stages of build_host_model (at the end).  One that can refuse the description returns the message, or null.
+// Every check that needs no table.
+inline const char *validate(const ss_model_desc &d) {
+  const int nb = d.nbody, nv = 6 + 3 * (nb - 1);
+  if (nb < 1 || nb > 63) return "nbody must be in [1,63]";
+  if (d.body_parent[0] != -1) return "body 0 must be the root";
+  for (int b = 1; b < nb; b++) if (d.body_parent[b] < 0 || d.body_parent[b] >= b) return "parents must precede children";
+  // bodies must come in depth-first order (the subtree of b is the index range [b, b + size): subtree_sum_tables): b's parent is
   // b - 1 or one of its ancestors
   for (int b = 2; b < nb; b++) {
     int a = b - 1;
     while (a > 0 && a != d.body_parent[b]) a = d.body_parent[a];
-    if (a != d.body_parent[b]) { out.error = "bodies must be in depth-first order"; return false; }
+    if (a != d.body_parent[b]) return "bodies must be in depth-first order";
   }
-
-  for (int i = 0; i < 6; i++)                              // the root solve treats the free joint as a plain 6x6 system
-    if (d.dof_armature[i] != 0.0) { out.error = "armature on the free joint is not supported"; return false; }
-  // ---- dof constants: arm, lo, hi, limited, invw, kp, kd, tlim, ascale, aoffset, actuated, pad
-  std::vector<real> dofc(nv * kDofC, real(0));
-  out.dof_act.assign(nv, -1);
+  // (the root solve treats the free joint as a plain 6x6 system)
+  for (int i = 0; i < 6; i++) if (d.dof_armature[i] != 0.0) return "armature on the free joint is not supported";
+  std::vector<bool> driven(nv, false);
   for (int i = 0; i < d.nu; i++) {
-    int dof = d.actuator_dof[i];
-    if (dof < 6 || dof >= nv || out.dof_act[dof] >= 0) { out.error = "bad actuator_dof"; return false; }
-    out.dof_act[dof] = i;
+    const int dof = d.actuator_dof[i];
+    if (dof < 6 || dof >= nv || driven[dof]) return "bad actuator_dof";
+    driven[dof] = true;
   }
+  for (int b = 0; b < nb; b++) if (d.geom_type[b] != SS_GEOM_BOX && d.geom_type[b] != SS_GEOM_CAPSULE && d.geom_type[b] != SS_GEOM_SPHERE) return "unknown geom type";
+  if (d.impratio != 1.0) return "impratio != 1 is not supported";
+  return nullptr;
+}
+
+// Node tree (node b + 1 = body b below the two nodes of the free joint) and every node's chain from the root, itself included at its depth.
+inline const char *node_tree(Tree &t) {
+  const int nb = (int)t.parent.size(), nn = nb + 1;
+  std::vector<int> nparent(nn); t.ndepth.assign(nn, 0);
+  nparent[0] = -1; nparent[1] = 0; t.ndepth[1] = 1;
+  for (int b = 1; b < nb; b++) { nparent[b + 1] = t.parent[b] + 1; t.ndepth[b + 1] = t.ndepth[t.parent[b] + 1] + 1; }
+  t.nlev = 1 + *std::max_element(t.ndepth.begin(), t.ndepth.end());
+  if (t.nlev > 32) return "tree too deep";
+  t.chainnode.assign(nn * t.nlev, 0);                      // row width: the number of levels
+  for (int n = 0; n < nn; n++)
+    for (int a = n; a >= 0; a = nparent[a]) t.chainnode[n * t.nlev + t.ndepth[a]] = a;
+  return nullptr;
+}
+
+// Subtree sums in two phases (ss_kernel.h subtree_sum).  Bodies are in depth-first order, so the subtree of b is the index range
+// [b, b + size).  Bodies whose subtree has <= 8 bodies sum their index range directly (one trip of 8 reads); the few large ones add
+// their own value, the finished sums of their small children and, recursively, the terms of their large children ("cover": index
+// t < 64 = input of body t, t >= 64 = phase-1 output of body t - 64; at most 63 entries per body, 63 x 63 < 4096 in all: the fields of sum_big hold them).
+inline void subtree_sum_tables(Tree &t) {
+  const int nb = (int)t.parent.size(), kSmall = 8;
+  std::vector<int> subsize(nb, 1), order(nb);
+  for (int b = nb - 1; b >= 1; b--) subsize[t.parent[b]] += subsize[b];
+  for (int b = 0; b < nb; b++) order[b] = b;
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return subsize[x] > subsize[y]; });
+  std::vector<std::vector<int>> cov(nb);
+  for (int b = nb - 1; b >= 0; b--) {                        // children before parents (depth-first order)
+    if (subsize[b] <= kSmall) continue;
+    cov[b].push_back(b);
+    for (int c = b + 1; c < nb; c++) {
+      if (t.parent[c] != b) continue;
+      if (subsize[c] <= kSmall) cov[b].push_back(64 + c);
+      else cov[b].insert(cov[b].end(), cov[c].begin(), cov[c].end());
+    }
+  }
+  for (int b : order) {
+    if (subsize[b] <= kSmall) { t.sum_small.push_back(b | (subsize[b] << 8)); continue; }
+    t.sum_big.push_back(b | ((int)t.sum_cover.size() << 8) | ((int)cov[b].size() << 20));
+    t.sum_cover.insert(t.sum_cover.end(), cov[b].begin(), cov[b].end());
+  }
+}
+
+// Elimination tree of the articulated-body sweeps (HdrC): the body tree re-rooted at its centre.  The root minimises the depth (ties:
+// the narrower widest level, then the lower index); the widest level may not exceed 16 nodes (two passes of 8 lane groups).
+// Picks the root and gives every body its level (dep) and its neighbour towards the root (tw, -1 for the root).
+inline int centre_of_tree(const Tree &t, std::vector<int> &dep, std::vector<int> &tw) {
+  const int nb = (int)t.parent.size();
+  std::vector<std::vector<int>> adj(nb);
+  for (int b = 1; b < nb; b++) { adj[b].push_back(t.parent[b]); adj[t.parent[b]].push_back(b); }
+  auto bfs = [&](int c) {
+    dep.assign(nb, -1); tw.assign(nb, -1);
+    std::vector<int> q{c}; dep[c] = 0;
+    for (size_t i = 0; i < q.size(); i++) for (int o : adj[q[i]]) if (dep[o] < 0) { dep[o] = dep[q[i]] + 1; tw[o] = q[i]; q.push_back(o); }
+  };
+  int best = 0, bestd = 1 << 30, bestw = 1 << 30;
+  for (int c = 0; c < nb; c++) {
+    bfs(c);
+    const int dmax = *std::max_element(dep.begin(), dep.end());
+    std::vector<int> wd(dmax + 1, 0); for (int b = 0; b < nb; b++) wd[dep[b]]++;
+    const int wmax = dmax ? *std::max_element(wd.begin() + 1, wd.end()) : 0;
+    if (wmax > 16) continue;
+    if (dmax < bestd || (dmax == bestd && wmax < bestw)) { best = c; bestd = dmax; bestw = wmax; }
+  }
+  bfs(best);
+  return best;
+}
+// Level lists: children of one node contiguous, in the order of their parents' positions; a node's children by falling height of
+// their subtrees (ties: body index) — the limbs' nodes then keep one slot from level to level and the leaves come last, which is
+// what lets the sweep towards the root keep a limb's rows in registers (hc.chain)
+inline std::vector<std::vector<int>> level_lists(int root, int nlev, const std::vector<int> &dep, const std::vector<int> &tw) {
+  const int nb = (int)dep.size();
+  std::vector<int> hgt(nb, 0);
+  for (int L = nlev; L >= 1; L--) for (int b = 0; b < nb; b++) if (dep[b] == L) hgt[tw[b]] = std::max(hgt[tw[b]], hgt[b] + 1);
+  std::vector<std::vector<int>> levb(nlev + 1);
+  levb[0].push_back(root);
+  for (int L = 1; L <= nlev; L++)
+    for (int pb : levb[L - 1]) {
+      std::vector<int> ch;
+      for (int b = 0; b < nb; b++) if (dep[b] == L && tw[b] == pb) ch.push_back(b);
+      std::stable_sort(ch.begin(), ch.end(), [&](int x, int y) { return hgt[x] > hgt[y]; });
+      levb[L].insert(levb[L].end(), ch.begin(), ch.end());
+    }
+  return levb;
+}
+// The level records and packed level properties of HdrC for that root, and the same per body (towards, joint, negated).
+inline const char *elimination_tree(Tree &t) {
+  const int nb = (int)t.parent.size();
+  std::vector<int> dep, tw;
+  HdrC &hc = t.hc;
+  hc.root = centre_of_tree(t, dep, tw);
+  hc.nlev = *std::max_element(dep.begin(), dep.end()); hc.pel_level = dep[0];
+  const int nlev = hc.nlev;
+  const std::vector<std::vector<int>> levb = level_lists(hc.root, nlev, dep, tw);
+  t.towards.assign(nb, 255); t.joint.assign(nb, 0); t.negated.assign(nb, 0);
+  int maxlev = 0; bool cpack_unrepresentable = false;
+  for (int L = 1; L <= nlev; L++) {
+    const int nk = (int)levb[L].size();
+    maxlev = std::max(maxlev, nk);
+    hc.nkpack[(L - 1) >> 4] |= (unsigned long long)(nk - 1) << (4 * ((L - 1) & 15));
+    int cmaxL = 0, slot = 0;
+    bool chainL = L < nlev;
+    for (int b : levb[L]) {
+      const int e = tw[b];                                    // neighbour towards the root
+      const bool kin = t.parent[b] == e;                      // walked along the kinematic direction: b's own joint
+      const int jn = (kin ? b : e) + 1;                       // node index of the joint on this edge (its dofs are 3 jn ..)
+      int cfirst = 0, cc = 0;
+      if (L < nlev)
+        for (int k2 = 0; k2 < (int)levb[L + 1].size(); k2++)
+          if (tw[levb[L + 1][k2]] == b) { if (cc == 0) cfirst = k2; cc++; }
+      t.towards[b] = e; t.joint[b] = jn; t.negated[b] = kin ? 0 : 1;
+      t.levrec.push_back(b | (jn << 8) | (e << 16) | ((kin ? 0 : 1) << 24) | ((b == 0 ? 1 : 0) << 25));
+      t.levrec.push_back(cfirst | (cc << 8));
+      if (!kin) hc.neg |= 1ull << (L - 1);
+      cmaxL = std::max(cmaxL, cc);
+      if (cc > 1 || (cc == 1 && cfirst != slot)) chainL = false;
+      slot++;
+    }
+    if (chainL) hc.chain |= 1ull << (L - 1);
+    // the fixed-layout instantiations read this as "most children of a node of level L" (3 bits per level): a tree with a node of
+    // more than 7 children below the root, or deeper than 21 levels, gets a value no instantiation is built for (runtime kernel)
+    if (L <= 21 && cmaxL <= 7) hc.cpack |= (unsigned long long)cmaxL << (3 * (L - 1));
+    else cpack_unrepresentable = true;
+  }
+  if (t.levrec.empty()) t.levrec.assign(2, 0);
+  if (cpack_unrepresentable) hc.cpack = ~0ull;
+  if (maxlev > 16) return "more than 16 nodes in one tree level";
+  t.maxlev = std::max(maxlev, 1);                            // sizes the level buffer of the LDS layout
+  return nullptr;
+}
+
+// Dof constants, the inverse weight column left zero.
+inline std::vector<real> dof_constants(const ss_model_desc &d) {
+  const int nv = 6 + 3 * (d.nbody - 1);
+  std::vector<int> dof_act(nv, -1);                         // actuator index of a dof or -1
+  for (int i = 0; i < d.nu; i++) dof_act[d.actuator_dof[i]] = i;
+  std::vector<real> dofc(nv * kDofC, real(0));
   for (int i = 0; i < nv; i++) {
     real *c = &dofc[i * kDofC];
-    c[0] = (real)d.dof_armature[i];
-    c[1] = (real)d.jnt_range[2 * i]; c[2] = (real)d.jnt_range[2 * i + 1];
+    c[0] = (real)d.dof_armature[i]; c[1] = (real)d.jnt_range[2 * i]; c[2] = (real)d.jnt_range[2 * i + 1];
     c[3] = (i >= 6 && d.jnt_limited[i]) ? 1.f : 0.f;
-    c[4] = (real)d.dof_invweight0[i];
-    int a = out.dof_act[i];
+    const int a = dof_act[i];
     if (a >= 0) {
       c[5] = (real)d.kp[a]; c[6] = (real)d.kd[a]; c[7] = (real)d.torque_lim[a];
       c[8] = (real)d.act_scale[a]; c[9] = (real)d.act_offset[a]; c[10] = 1.f; c[11] = (real)a;
     } else c[11] = -1.f;
   }
+  return dofc;
+}
 
-  // ---- body constants (registers): off3 ipos3 mass Ibody(xx xy xz yy yz zz) invw_tr
-  out.bodyc.assign(nb * kBodyC, real(0));
+// Body constants (registers): off3 ipos3 mass Ibody(xx xy xz yy yz zz) invw_tr; the dof inverse weights; the body offsets; meaninertia.
+inline const char *body_constants(const ss_model_desc &d, Shape &s) {
+  const int nb = d.nbody, nv = 6 + 3 * (nb - 1);
+  // mjModel.stat.meaninertia; <= 0 (e.g. a caller of the pre-round-3 struct, zero-initialised): computed here from the description
+  s.meaninertia = d.meaninertia > 0.0 ? d.meaninertia : meaninertia_at_qpos0(d);
+  if (!(s.meaninertia > 0.0)) return "meaninertia: the inertia matrix at qpos0 has no positive diagonal";
+  s.bodyc.assign(nb * kBodyC, real(0)); s.boff.assign(3 * nb, real(0));
+  s.invw.assign(d.dof_invweight0, d.dof_invweight0 + nv);
   for (int b = 0; b < nb; b++) {
-    real *c = &out.bodyc[b * kBodyC];
-    for (int k = 0; k < 3; k++) { c[k] = (real)d.body_pos[3 * b + k]; c[3 + k] = (real)d.body_ipos[3 * b + k]; }
+    real *c = &s.bodyc[b * kBodyC];
+    // (the root's offset is its initial position, not a parent-frame offset: left zero)
+    for (int k = 0; k < 3; k++) { c[k] = s.boff[3 * b + k] = b == 0 ? real(0) : (real)d.body_pos[3 * b + k]; c[3 + k] = (real)d.body_ipos[3 * b + k]; }
     c[6] = (real)d.body_mass[b];
-    double R[9]; quat2mat(d.body_iquat + 4 * b, R);
-    double I[9];
-    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) {
-      double s = 0; for (int k = 0; k < 3; k++) s += R[3 * i + k] * d.body_inertia[3 * b + k] * R[3 * j + k];
-      I[3 * i + j] = s;
-    }
+    double I[9]; body_frame_inertia(d, b, I);
     c[7] = (real)I[0]; c[8] = (real)I[1]; c[9] = (real)I[2]; c[10] = (real)I[4]; c[11] = (real)I[5]; c[12] = (real)I[8];
     c[13] = (real)d.body_invweight0[2 * b];
   }
-  // root offset is the initial position, not a parent-frame offset
-  out.bodyc[0] = out.bodyc[1] = out.bodyc[2] = 0.f;
+  return nullptr;
+}
 
-  // ---- contact candidates: boxes first (8 corners each, 8-aligned), then capsule ends
-  out.candc.clear(); out.candb.clear();
+// Floor-contact candidates: boxes first (8 corners each, 8-aligned), then two per capsule or sphere; the counts that follow from them.
+inline void floor_candidates(const ss_model_desc &d, Topology &t, Shape &s) {
+  const int nb = d.nbody; Hdr &h = t.h;
   for (int b = 0; b < nb; b++) {
     if (d.geom_type[b] != SS_GEOM_BOX) continue;
     double G[9]; quat2mat(d.geom_quat + 4 * b, G);
     for (int i = 0; i < 8; i++) {
-      double v[3] = {(i & 1) ? d.geom_size[3 * b] : -d.geom_size[3 * b], (i & 2) ? d.geom_size[3 * b + 1] : -d.geom_size[3 * b + 1],
-                     (i & 4) ? d.geom_size[3 * b + 2] : -d.geom_size[3 * b + 2]};
+      const double *z = d.geom_size + 3 * b, v[3] = {(i & 1) ? z[0] : -z[0], (i & 2) ? z[1] : -z[1], (i & 4) ? z[2] : -z[2]};
       real c[kCandC] = {0};
       for (int r = 0; r < 3; r++) {
         c[r] = (real)(G[3 * r] * v[0] + G[3 * r + 1] * v[1] + G[3 * r + 2] * v[2]);    // corner vector (body frame)
         c[3 + r] = (real)d.geom_pos[3 * b + r];                                         // box centre (body frame)
       }
       c[7] = (real)d.body_invweight0[2 * b];
-      out.candc.insert(out.candc.end(), c, c + kCandC); out.candb.push_back(b);
+      s.candc.insert(s.candc.end(), c, c + kCandC); t.candb.push_back(b);
     }
+    h.nbox++;
   }
   for (int b = 0; b < nb; b++) {
     if (d.geom_type[b] == SS_GEOM_BOX) continue;
-    if (d.geom_type[b] != SS_GEOM_CAPSULE && d.geom_type[b] != SS_GEOM_SPHERE) { out.error = "unknown geom type"; return false; }
     const bool sphere = d.geom_type[b] == SS_GEOM_SPHERE;    // a capsule of zero half length: ONE floor contact (mjc_PlaneSphere), no tangent hint
     double G[9]; quat2mat(d.geom_quat + 4 * b, G);
-    for (int s = 0; s < 2; s++) {
-      double sg = s ? -1.0 : 1.0;
+    for (int e = 0; e < 2; e++) {
+      double sg = e ? -1.0 : 1.0;
       real c[kCandC] = {0};
       for (int r = 0; r < 3; r++) {
         c[r] = (real)(d.geom_pos[3 * b + r] + (sphere ? 0.0 : sg * G[3 * r + 2] * d.geom_size[3 * b + 1]));   // end-sphere centre (body frame)
         c[3 + r] = sphere ? real(0) : (real)G[3 * r + 2];                                    // capsule axis (body frame): the first tangent's hint
       }
       // (the slot pairing of the solver wants two candidates per non-box body: a sphere's second one has a radius that never qualifies)
-      c[6] = (sphere && s == 1) ? real(-1e30) : (real)d.geom_size[3 * b];                    // radius
+      c[6] = (sphere && e == 1) ? real(-1e30) : (real)d.geom_size[3 * b];                    // radius
       c[7] = (real)d.body_invweight0[2 * b];
-      out.candc.insert(out.candc.end(), c, c + kCandC); out.candb.push_back(b | 256);
+      s.candc.insert(s.candc.end(), c, c + kCandC); t.candb.push_back(b | 256);
     }
   }
-  h.ncand = (int)out.candb.size();
-  h.nbox = 0;
-  for (int b = 0; b < nb; b++) h.nbox += d.geom_type[b] == SS_GEOM_BOX;
+  h.ncand = (int)t.candb.size();
   h.nslot = 4 * h.nbox + 2 * (nb - h.nbox);
-  out.legal.assign(nb, 0);
-  out.illegal_mask = 0;
-  for (int b = 0; b < nb; b++) {
-    out.legal[b] = d.legal_contact ? d.legal_contact[b] : 0;
-    if (!out.legal[b]) out.illegal_mask |= (1ull << b);
-  }
+  for (int b = 0; b < nb; b++)
+    if (!(d.legal_contact && d.legal_contact[b])) t.illegal_mask |= 1ull << b;
+}
 
-  // ---- shared blob (copied into LDS once per workgroup)
-  if (nlev > 32) { out.error = "tree too deep"; return false; }
-  int maxlev = 0;                                           // widest level of the elimination tree (below)
-  auto &S = out.shared; S.clear();
-  auto push_i = [&](const std::vector<int> &v) { int o = (int)S.size(); for (int x : v) S.push_back((uint32_t)x); return o; };
-  std::vector<real> Sf;                                    // real-valued tables, appended behind the integer ones below (assembled there)
-  std::vector<real> boffv;                                 // body frame offsets in the parent frame (chain walk of forward_kin)
-  for (int b = 0; b < nb; b++) for (int k = 0; k < 3; k++) boffv.push_back(b == 0 ? real(0) : (real)d.body_pos[3 * b + k]);
-  h.o_chainnode = push_i(chainnode);
-  h.o_ndepth = push_i(ndepth);
-  std::vector<int> bpar(d.body_parent, d.body_parent + nb);
-  h.o_bparent = push_i(bpar);
-  {
-    // subtree sizes: bodies are in depth-first order, so the subtree of b is the index range [b, b + size)
-    std::vector<int> subsize(nb, 1);
-    for (int b = nb - 1; b >= 1; b--) subsize[d.body_parent[b]] += subsize[b];
-    for (int b = 0; b < nb; b++) {
-      for (int c = b + 1; c < b + subsize[b]; c++) {
-        int a = c; while (a > b) a = d.body_parent[a];
-        if (a != b) { out.error = "bodies must be in depth-first order"; return false; }
-      }
-    }
-    // subtree sums in two phases (ss_kernel.h subtree_sum): bodies whose subtree has <= 8 bodies sum their index range
-    // directly (one trip of 8 reads); the few large ones add their own value, the finished sums of their small children
-    // and, recursively, the terms of their large children ("cover": index t < 64 = input of body t, t >= 64 = phase-1
-    // output of body t - 64).
-    const int kSmall = 8;
-    std::vector<int> small_l, big_l, cover;
-    std::vector<int> order(nb);
-    for (int b = 0; b < nb; b++) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return subsize[x] > subsize[y]; });
-    for (int b : order) if (subsize[b] <= kSmall) small_l.push_back(b | (subsize[b] << 8));
-    std::vector<std::vector<int>> cov(nb);
-    for (int b = nb - 1; b >= 0; b--) {                        // children before parents (depth-first order)
-      if (subsize[b] <= kSmall) continue;
-      cov[b].push_back(b);
-      for (int c = b + 1; c < nb; c++) {
-        if (d.body_parent[c] != b) continue;
-        if (subsize[c] <= kSmall) cov[b].push_back(64 + c);
-        else cov[b].insert(cov[b].end(), cov[c].begin(), cov[c].end());
-      }
-    }
-    for (int b : order) {
-      if (subsize[b] <= kSmall) continue;
-      if (cov[b].size() > 255 || cover.size() > 4095) { out.error = "subtree cover table overflow"; return false; }
-      big_l.push_back(b | ((int)cover.size() << 8) | ((int)cov[b].size() << 20));
-      cover.insert(cover.end(), cov[b].begin(), cov[b].end());
-    }
-    h.n_sumsmall = (int)small_l.size(); h.n_sumbig = (int)big_l.size();
-    h.o_sumsmall = push_i(small_l); h.o_sumbig = push_i(big_l); h.o_sumcover = push_i(cover);
-  }
-  {
-    // ---- elimination tree of the articulated-body sweeps (HdrC): the body tree re-rooted at its centre.  The root minimises the
-    // depth (ties: the narrower widest level, then the lower index); the widest level may not exceed 16 nodes (two passes of 8
-    // lane groups)
-    std::vector<std::vector<int>> adj(nb);
-    for (int b = 1; b < nb; b++) { adj[b].push_back(d.body_parent[b]); adj[d.body_parent[b]].push_back(b); }
-    auto bfs = [&](int c, std::vector<int> &dep, std::vector<int> &towards) {
-      dep.assign(nb, -1); towards.assign(nb, -1);
-      std::vector<int> q{c}; dep[c] = 0;
-      for (size_t i = 0; i < q.size(); i++) for (int o : adj[q[i]]) if (dep[o] < 0) { dep[o] = dep[q[i]] + 1; towards[o] = q[i]; q.push_back(o); }
-    };
-    int best = 0, bestd = 1 << 30, bestw = 1 << 30;
-    std::vector<int> dep, tw;
-    for (int c = 0; c < nb; c++) {
-      bfs(c, dep, tw);
-      int dmax = 0; for (int b = 0; b < nb; b++) dmax = std::max(dmax, dep[b]);
-      std::vector<int> wd(dmax + 1, 0); for (int b = 0; b < nb; b++) wd[dep[b]]++;
-      int wmax = 0; for (int L = 1; L <= dmax; L++) wmax = std::max(wmax, wd[L]);
-      if (wmax > 16) continue;
-      if (dmax < bestd || (dmax == bestd && wmax < bestw)) { best = c; bestd = dmax; bestw = wmax; }
-    }
-    bfs(best, dep, tw);
-    bestd = 0; for (int b = 0; b < nb; b++) bestd = std::max(bestd, dep[b]);
-    HdrC &hc = out.hc;
-    hc.root = best; hc.nlev = bestd; hc.pel_level = dep[0]; hc.nkpack[0] = hc.nkpack[1] = 0ull; hc.cpack = 0ull;
-    if (bestd > 32) { out.error = "tree too deep"; return false; }
-    // level lists: children of one node contiguous, in the order of their parents' positions; a node's children by falling height of
-    // their subtrees (ties: body index) — the limbs' nodes then keep one slot from level to level and the leaves come last, which is
-    // what lets the sweep towards the root keep a limb's rows in registers (hc.chain)
-    std::vector<int> hgt(nb, 0);
-    for (int L = bestd; L >= 1; L--) for (int b = 0; b < nb; b++) if (dep[b] == L) hgt[tw[b]] = std::max(hgt[tw[b]], hgt[b] + 1);
-    std::vector<std::vector<int>> levb(bestd + 1);
-    levb[0].push_back(best);
-    for (int L = 1; L <= bestd; L++)
-      for (int pb_ : levb[L - 1]) {
-        std::vector<int> ch;
-        for (int b = 0; b < nb; b++) if (dep[b] == L && tw[b] == pb_) ch.push_back(b);
-        std::stable_sort(ch.begin(), ch.end(), [&](int x, int y) { return hgt[x] > hgt[y]; });
-        for (int b : ch) levb[L].push_back(b);
-      }
-    hc.chain = 0ull; hc.neg = 0ull;
-    std::vector<int> rec;
-    bool cpack_unrepresentable = false;
-    for (int L = 1; L <= bestd; L++) {
-      const int nk = (int)levb[L].size();
-      maxlev = std::max(maxlev, nk);
-      hc.nkpack[(L - 1) >> 4] |= (unsigned long long)(nk - 1) << (4 * ((L - 1) & 15));
-      int cmaxL = 0, slot_ = 0;
-      bool chainL = L < bestd;
-      for (int b : levb[L]) {
-        const int e = tw[b];                                    // neighbour towards the root
-        const bool kin = d.body_parent[b] == e;                 // walked along the kinematic direction: b's own joint
-        const int jn = (kin ? b : e) + 1;                       // node index of the joint on this edge (its dofs are 3 jn ..)
-        int cfirst = 0, cc = 0;
-        if (L < bestd)
-          for (int k2 = 0; k2 < (int)levb[L + 1].size(); k2++)
-            if (tw[levb[L + 1][k2]] == b) { if (cc == 0) cfirst = k2; cc++; }
-        rec.push_back(b | (jn << 8) | (e << 16) | ((kin ? 0 : 1) << 24) | ((b == 0 ? 1 : 0) << 25));
-        if (!kin) hc.neg |= 1ull << (L - 1);
-        rec.push_back(cfirst | (cc << 8));
-        cmaxL = std::max(cmaxL, cc);
-        if (cc > 1 || (cc == 1 && cfirst != slot_)) chainL = false;
-        slot_++;
-      }
-      if (chainL) hc.chain |= 1ull << (L - 1);
-      // the fixed-layout instantiations read this as "most children of a node of level L" (3 bits per level): a tree with a node of
-      // more than 7 children below the root, or deeper than 21 levels, gets a value no instantiation is built for (runtime kernel)
-      if (L <= 21 && cmaxL <= 7) hc.cpack |= (unsigned long long)cmaxL << (3 * (L - 1));
-      else cpack_unrepresentable = true;
-    }
-    if (rec.empty()) { rec.push_back(0); rec.push_back(0); }
-    if (cpack_unrepresentable) hc.cpack = ~0ull;
-    hc.o_lev = push_i(rec);
-    if (maxlev > 16) { out.error = "more than 16 nodes in one tree level"; return false; }
-    if (maxlev < 1) maxlev = 1;
-    h.maxlev = maxlev;                                        // sizes the level buffer of the LDS layout
-  }
-  // The SMPL-X size class (more than 32 bodies: LDS, not the register file, caps its resident envs; round 5) runs LEAN: the aliased
-  // env-slice layout (ss_hdr.h make_layout) and the dof-constant table left in global memory — 12 reals per dof = 7.6 KB of the
-  // workgroup's LDS for 52 bodies, read once or twice per mj_step per lane (limits, Stable PD: L1-resident), except the armature, which
-  // the Newton iteration reads and which keeps a column of its own in LDS.  Together with the action read from global memory instead
-  // of an LDS copy that is a seventh resident env per CU.  The LDS copy of the blob is its prefix of h.shared_words words; the dof
-  // table lies behind it.
-  const bool alias = nb > 32 && alias_layout_fits(nb, maxlev, h.nslot) && !std::getenv("SS_NO_ALIAS_LAYOUT");
-  int lds_reals, o_arm = 0;
-  if (alias) {
-    h.o_boff = (int)Sf.size(); Sf.insert(Sf.end(), boffv.begin(), boffv.end());
-    o_arm = (int)Sf.size(); for (int i = 0; i < nv; i++) Sf.push_back(dofc[i * kDofC]);
-    while (Sf.size() % 4) Sf.push_back(real(0));
-    lds_reals = (int)Sf.size();
-    h.o_dofc = (int)Sf.size(); Sf.insert(Sf.end(), dofc.begin(), dofc.end());
-  } else {
-    h.o_dofc = (int)Sf.size(); Sf.insert(Sf.end(), dofc.begin(), dofc.end());
-    h.o_boff = (int)Sf.size(); Sf.insert(Sf.end(), boffv.begin(), boffv.end());
-    lds_reals = (int)Sf.size();
-  }
-  while (S.size() % 4) S.push_back(0u);                     // reals start 16-byte aligned
-  out.o_real = (int)S.size();
-  S.resize(S.size() + Sf.size() * (sizeof(real) / 4));
-  std::memcpy(S.data() + out.o_real, Sf.data(), Sf.size() * sizeof(real));
-  h.shared_words = out.o_real + lds_reals * (int)(sizeof(real) / 4);   // what a workgroup copies into LDS (the whole blob unless lean)
-  const int real0 = out.o_real / (int)(sizeof(real) / 4);   // kernel-side offsets count reals from the start of the blob
-  h.o_dofc += real0; h.o_boff += real0;
-  h.arm_lean = (unsigned long long)(uint32_t)(alias ? o_arm + real0 : 0) | ((unsigned long long)(alias ? 1 : 0) << 32);
-
-  // ---- per-env LDS layout (floats); arrays with disjoint lifetimes share storage (LDS capacity sets the number
-  // of resident envs per CU)
-  if (nn > 64) { out.error = "too many nodes"; return false; }
-  // The SMPL-X size class (more than 32 bodies: LDS, not the register file, caps its resident envs) gets the aliased layout when its
-  // records fit (ss_hdr.h make_layout); body-body-contact batches of such a model run on the plain one (h_sc), whose Aown .. (W, y)
-  // stretch holds their dense system.
-  auto fill = [&](Hdr &g, const Layout &y) {
-    g.l_q = y.l_q; g.l_v = y.l_v; g.l_a = y.l_a; g.l_tau = y.l_tau; g.l_Fb = y.l_Fb; g.l_act = y.l_act; g.l_delta = y.l_delta; g.l_Pb = y.l_Pb; g.l_V = y.l_V;
-    g.l_diag = y.l_diag; g.l_S = y.l_S; g.l_Ab = y.l_Ab; g.l_Iown = y.l_Iown; g.l_An = y.l_An; g.l_Aown = y.l_Aown; g.ia_stride = y.ia_stride;
-    g.l_IA = y.l_IA; g.l_Gb = y.l_Gb; g.l_tmp = y.l_tmp; g.l_Ubuf = y.l_Ubuf; g.l_Wst = y.l_Wst; g.l_R = y.l_R; g.l_r = y.l_r;
-    g.a_stride = y.a_stride; g.l_Rloc = y.l_Rloc; g.l_w2 = y.l_w2;
-    g.env_floats = y.env_floats;
+// Body-body collision: candidate pairs (mj_collision's static filters: contype / conaffinity masks, parent-child filter, <exclude>
+// pairs) and the geom table of the pair functions.  The pair's first geom is the one MuJoCo hands to the pair function first (the
+// lower type id: sphere 2 < capsule 3 < box 6, then the lower geom id); contact normals point from it to the second.
+inline void pair_and_geom_tables(const ss_model_desc &d, Topology &t, Shape &s) {
+  const int nb = d.nbody;
+  auto rank = [&](int b) { return d.geom_type[b] == SS_GEOM_SPHERE ? 0 : (d.geom_type[b] == SS_GEOM_CAPSULE ? 1 : 2); };
+  // bounding spheres about the geom centres: half diagonal of a box, radius + half length of a capsule
+  auto reach = [&](int b) {
+    const double *z = d.geom_size + 3 * b;
+    return d.geom_type[b] == SS_GEOM_BOX ? std::sqrt(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]) : z[0] + (d.geom_type[b] == SS_GEOM_SPHERE ? 0.0 : z[1]);
   };
-  {
-    const Layout y = make_layout(nb, maxlev, false);
-    fill(h, y);
-    if (13 * h.nslot > h.l_Wst - h.l_An) { out.error = "contact record buffer does not fit"; return false; }
-    if (alias) fill(h, make_layout(nb, maxlev, true));
-  }
-
-  // ---- body-body collision: candidate pairs (mj_collision's static filters: contype / conaffinity masks, parent-child
-  // filter, <exclude> pairs) and the geom table of the pair functions.  The pair's first geom is the one MuJoCo hands to the
-  // pair function first (capsule before box, then the lower id); contact normals point from it to the second.
-  out.pairs.clear();
   for (int i = 0; i < nb; i++) for (int j = i + 1; j < nb; j++) {
     const int ct1 = d.geom_contype ? d.geom_contype[i] : 1, ca1 = d.geom_conaffinity ? d.geom_conaffinity[i] : 1;
     const int ct2 = d.geom_contype ? d.geom_contype[j] : 1, ca2 = d.geom_conaffinity ? d.geom_conaffinity[j] : 1;
@@ -407,68 +361,155 @@ inline bool build_host_model(const ss_model_desc &d, HostModel &out) {
     for (int e = 0; e < d.nexclude; e++)
       ex |= (d.exclude[2 * e] == i && d.exclude[2 * e + 1] == j) || (d.exclude[2 * e] == j && d.exclude[2 * e + 1] == i);
     if (ex) continue;
-    // MuJoCo hands the geom of the lower type id to the pair function first (sphere 2 < capsule 3 < box 6), the lower geom id among equals
-    auto rank = [&](int b) { return d.geom_type[b] == SS_GEOM_SPHERE ? 0 : (d.geom_type[b] == SS_GEOM_CAPSULE ? 1 : 2); };
     const int first = rank(j) < rank(i) ? j : i;
-    out.pairs.push_back(first | ((first == i ? j : i) << 8));
-    // bounding spheres about the geom centres: half diagonal of a box, radius + half length of a capsule; a hair of slack so that
-    // the float rounding of the sum can never prune a pair the pair function would report (those are strictly inside)
-    auto reach = [&](int b) {
-      const double *z = d.geom_size + 3 * b;
-      return d.geom_type[b] == SS_GEOM_BOX ? std::sqrt(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]) : z[0] + (d.geom_type[b] == SS_GEOM_SPHERE ? 0.0 : z[1]);
-    };
+    t.pair_ids.push_back(first | ((first == i ? j : i) << 8));
+    // a hair of slack so that the float rounding of the sum can never prune a pair the pair function would report (those are strictly inside)
     const float rs = (float)((reach(i) + reach(j) + d.margin) * (1.0 + 1e-5));
     int32_t bits; std::memcpy(&bits, &rs, 4);
-    out.pairs.push_back(bits);
+    s.reach.push_back(bits);
   }
-  out.geomc.assign((size_t)nb * kGeomC, real(0));
+  s.geomc.assign((size_t)nb * kGeomC, real(0));
   for (int b = 0; b < nb; b++) {
-    real *c = &out.geomc[(size_t)b * kGeomC];
+    real *c = &s.geomc[(size_t)b * kGeomC];
     double G[9]; quat2mat(d.geom_quat + 4 * b, G);
     for (int k = 0; k < 3; k++) { c[k] = (real)d.geom_pos[3 * b + k]; c[3 + k] = (real)d.geom_size[3 * b + k]; }
     if (d.geom_type[b] == SS_GEOM_SPHERE) { c[4] = 0; c[5] = 0; }                                // half length 0 whatever the caller left there
     for (int k = 0; k < 9; k++) c[6 + k] = (real)G[k];
     c[15] = (real)d.geom_type[b];
   }
-  {
-    const Layout yp = make_layout(nb, maxlev, false);
-    out.sc = make_layout_sc(nb, yp.env_floats, yp.l_An);
-  }
-  out.sc.npair = (int)out.pairs.size() / 2;
-  // per body of the elimination tree (SELFCOL kernels copy this into the env's LDS slice): neighbour towards the root (255: it is the
-  // root) | joint node << 8 | (S negated) << 16, and the mask of the bodies on its way to the root (itself included, the root not)
-  {
-    const HdrC &hc = out.hc;
-    std::vector<int> tw(nb, 255), jn(nb, 0), ng(nb, 0);
-    const uint32_t *rec = out.shared.data() + hc.o_lev;
-    for (int i = 0; i < nb - 1; i++) {
-      const int e0 = (int)rec[2 * i], b = e0 & 255;
-      tw[b] = (e0 >> 16) & 255; jn[b] = (e0 >> 8) & 255; ng[b] = (e0 >> 24) & 1;
-    }
-    out.sctab.assign(3 * nb, 0);
-    for (int b = 0; b < nb; b++) {
-      unsigned long long pm = 0ull;
-      for (int a = b; a != hc.root; a = tw[a]) pm |= 1ull << a;
-      out.sctab[3 * b] = tw[b] | (jn[b] << 8) | (ng[b] << 16);
-      out.sctab[3 * b + 1] = (int32_t)(uint32_t)(pm & 0xFFFFFFFFull); out.sctab[3 * b + 2] = (int32_t)(uint32_t)(pm >> 32);
-    }
-  }
-  if (nb < 2) out.self_collision_unavailable = "a single body has no body-body contacts";
-  // the dense assembly keeps 12 reals per joint between a contact's two bodies (at most 2 x levels of them) in the 6 nb reals of gc + zb
-  else if (8 * out.hc.nlev > 64) out.self_collision_unavailable = "elimination tree deeper than 8 levels (one lane per (joint, row) of a contact's joints)";
-  else if (12 * 2 * out.hc.nlev > out.sc.l_tab - out.sc.l_gc) out.self_collision_unavailable = "tree too deep for its body count (body-body contacts need 4 x levels <= bodies)";
+}
 
+inline void physics_scalars(const ss_model_desc &d, Hdr &h) {
   h.dt = (real)d.timestep; h.grav = (real)d.gravity; h.margin = (real)d.margin; h.mu = (real)d.friction;
   for (int k = 0; k < 5; k++) h.solimp[k] = (real)d.solimp[k];
-  double dmax = d.solimp[1];
-  double tc = d.solref[0] < 2 * d.timestep ? 2 * d.timestep : d.solref[0];
+  const double dmax = d.solimp[1], tc = d.solref[0] < 2 * d.timestep ? 2 * d.timestep : d.solref[0];
   h.K = (real)(1.0 / (dmax * dmax * tc * tc * d.solref[1] * d.solref[1]));
   h.B = (real)(2.0 / (dmax * tc));
   for (int k = 0; k < 3; k++) h.qpos0_root[k] = (real)d.qpos0[k];
-  if (d.impratio != 1.0) { out.error = "impratio != 1 is not supported"; return false; }
-  out.h_sc = h;
-  fill(out.h_sc, make_layout(nb, maxlev, false));
-  return true;
+}
+
+// One description as its two parts.  like: the topology of the model's shape 0, whose tree tables serve every shape with its parents.
+inline const char *describe(const ss_model_desc &d, const Topology *like, Topology &t, Shape &s) {
+  if (const char *e = validate(d)) return e;
+  const int nb = d.nbody;
+  Hdr &h = t.h;
+  h.nb = nb; h.nn = nb + 1; h.nv = 6 + 3 * (nb - 1); h.nq = h.nv + 1; h.nu = d.nu;
+  t.tree.parent.assign(d.body_parent, d.body_parent + nb);
+  if (!like || like->tree.parent != t.tree.parent) {
+    if (const char *e = node_tree(t.tree)) return e;
+    subtree_sum_tables(t.tree);
+    if (const char *e = elimination_tree(t.tree)) return e;
+  }
+  t.dofc = dof_constants(d);
+  if (const char *e = body_constants(d, s)) return e;
+  floor_candidates(d, t, s);
+  pair_and_geom_tables(d, t, s);
+  physics_scalars(d, h);
+  return nullptr;
+}
+
+// Everything but the geometry must agree: tree, joints, limits, gains, actuators, geom types, contact set, options.  The tables are
+// compared as the device gets them: rounded to `real`, bit for bit.
+inline bool same_topology(const Topology &a, const Topology &b) {
+  const Hdr &h = a.h, &g = b.h;
+  return h.nb == g.nb && h.nu == g.nu && h.ncand == g.ncand && h.nbox == g.nbox && h.nslot == g.nslot && a.tree.parent == b.tree.parent &&
+         a.dofc.size() == b.dofc.size() && !std::memcmp(a.dofc.data(), b.dofc.data(), a.dofc.size() * sizeof(real)) && a.candb == b.candb &&
+         a.pair_ids == b.pair_ids && a.illegal_mask == b.illegal_mask && h.dt == g.dt && h.grav == g.grav && h.margin == g.margin && h.mu == g.mu &&
+         h.K == g.K && h.B == g.B;
+}
+
+// The shared blob (copied into LDS once per workgroup) and its offsets in h and hc: the integer tables, then, 16-byte aligned, the real-valued ones — the
+// dof constants and the body offsets, with the shape's inverse weights and offsets, or zeros for a model of several shapes (read per env from bodyc).
+// lean (the SMPL-X size class, where LDS, not the register file, caps the resident envs; goes with the aliased layout of ss_hdr.h make_layout): the
+// dof-constant table stays in global memory — 12 reals per dof = 7.6 KB of the workgroup's LDS for 52 bodies, read once or twice per mj_step per lane
+// (limits, Stable PD: L1-resident), except the armature, which the Newton iteration reads and which keeps a column of its own in LDS.  Together with the
+// action read from global memory that is a seventh resident env per CU.  The LDS copy of the blob is its prefix of h.shared_words words; the dof table lies behind it.
+inline std::vector<uint32_t> assemble_blob(const Topology &t, const Shape *shape, bool lean, Hdr &h, HdrC &hc) {
+  std::vector<uint32_t> S;
+  auto push_i = [&](const std::vector<int> &v) { int o = (int)S.size(); S.insert(S.end(), v.begin(), v.end()); return o; };
+  const Tree &tr = t.tree;
+  h.o_chainnode = push_i(tr.chainnode); h.o_ndepth = push_i(tr.ndepth); h.o_bparent = push_i(tr.parent);
+  h.o_sumsmall = push_i(tr.sum_small); h.o_sumbig = push_i(tr.sum_big); h.o_sumcover = push_i(tr.sum_cover);
+  hc.o_lev = push_i(tr.levrec);
+  while (S.size() % 4) S.push_back(0u);                     // reals start 16-byte aligned
+  const int o_real = (int)S.size(), real0 = o_real / (int)(sizeof(real) / 4);   // kernel-side offsets count reals from the start of the blob
+  std::vector<real> dofc = t.dofc, boff(3 * h.nb, real(0)), F;
+  if (shape) { boff = shape->boff; for (int i = 0; i < h.nv; i++) dofc[i * kDofC + 4] = shape->invw[i]; }
+  auto push_r = [&](const std::vector<real> &v) { int o = real0 + (int)F.size(); F.insert(F.end(), v.begin(), v.end()); return o; };
+  int o_arm = 0;
+  if (lean) {
+    h.o_boff = push_r(boff);
+    o_arm = real0 + (int)F.size(); for (int i = 0; i < h.nv; i++) F.push_back(dofc[i * kDofC]);
+    while (F.size() % 4) F.push_back(real(0));
+  } else {
+    h.o_dofc = push_r(dofc); h.o_boff = push_r(boff);
+  }
+  h.shared_words = o_real + (int)F.size() * (int)(sizeof(real) / 4);   // what a workgroup copies into LDS (the whole blob unless lean)
+  if (lean) h.o_dofc = push_r(dofc);
+  h.arm_lean = (unsigned long long)(uint32_t)o_arm | ((unsigned long long)(lean ? 1 : 0) << 32);
+  S.resize(o_real + F.size() * (sizeof(real) / 4));
+  std::memcpy(S.data() + o_real, F.data(), F.size() * sizeof(real));
+  return S;
+}
+
+// One more block of the per-shape tables.  shaped (a model of several shapes): the block of bodyc ends in the dof inverse weights (shape_stride).
+inline void append_shape(const Topology &t, const Shape &s, bool shaped, HostModel &out) {
+  out.bodyc.insert(out.bodyc.end(), s.bodyc.begin(), s.bodyc.end());
+  if (shaped) { out.bodyc.insert(out.bodyc.end(), s.invw.begin(), s.invw.end()); out.bodyc.resize(out.bodyc.size() + (4 - s.invw.size() % 4) % 4, real(0)); }
+  out.candc.insert(out.candc.end(), s.candc.begin(), s.candc.end());
+  out.geomc.insert(out.geomc.end(), s.geomc.begin(), s.geomc.end());
+  for (size_t i = 0; i < s.reach.size(); i++) { out.pairs.push_back(t.pair_ids[i]); out.pairs.push_back(s.reach[i]); }
+}
+
+// Per-env LDS layouts (floats) of h, h_sc (= h but for its layout) and sc.  The SMPL-X size class gets the aliased one when its records fit
+// (ss_hdr.h make_layout); body-body-contact batches of such a model run on the plain one, whose Aown .. (W, y) stretch holds their dense system.
+inline const char *lds_layouts(bool alias, HostModel &m) {
+  const Layout plain = make_layout(m.h.nb, m.h.maxlev, false);
+  if (13 * m.h.nslot > plain.l_Wst - plain.l_An) return "contact record buffer does not fit";
+  m.h_sc = m.h; apply_layout(m.h_sc, plain);
+  apply_layout(m.h, alias ? make_layout(m.h.nb, m.h.maxlev, true) : plain);
+  m.sc = make_layout_sc(m.h.nb, plain.env_floats, plain.l_An);
+  return nullptr;
+}
+
+// Body-body contacts: behind the pair table, per body of the elimination tree (SELFCOL kernels copy this into the env's LDS slice) neighbour
+// towards the root (255: it is the root) | joint node << 8 | (S negated) << 16, and the mask of the bodies on its way to the root (itself
+// included, the root not); and whether the model can have them.
+inline void body_contact_tables(const Topology &top, HostModel &m) {
+  const Tree &t = top.tree; const int nb = m.h.nb;
+  m.sc.npair = (int)top.pair_ids.size(); m.sc.o_sctab = (int)m.pairs.size();
+  for (int b = 0; b < nb; b++) {
+    unsigned long long pm = 0ull;
+    for (int a = b; a != t.hc.root; a = t.towards[a]) pm |= 1ull << a;
+    m.pairs.push_back(t.towards[b] | (t.joint[b] << 8) | (t.negated[b] << 16));
+    m.pairs.push_back((int32_t)(uint32_t)(pm & 0xFFFFFFFFull)); m.pairs.push_back((int32_t)(uint32_t)(pm >> 32));
+  }
+  if (nb < 2) m.self_collision_unavailable = "a single body has no body-body contacts";
+  // the dense assembly keeps 12 reals per joint between a contact's two bodies (at most 2 x levels of them) in the 6 nb reals of gc + zb
+  else if (8 * t.hc.nlev > 64) m.self_collision_unavailable = "elimination tree deeper than 8 levels (one lane per (joint, row) of a contact's joints)";
+  else if (12 * 2 * t.hc.nlev > m.sc.l_tab - m.sc.l_gc) m.self_collision_unavailable = "tree too deep for its body count (body-body contacts need 4 x levels <= bodies)";
+}
+
+// The model of num_shapes descriptions of one humanoid with different body shapes (1: the plain case).  plain_layout: never the aliased
+// LDS layout and the lean tables (SS_NO_ALIAS_LAYOUT).  Returns the message of a refusal, or "".
+inline std::string build_host_model(const ss_model_desc *d, int num_shapes, bool plain_layout, HostModel &out) {
+  Topology top; Shape first;                                // of shape 0
+  for (int s = 0; s < num_shapes; s++) {
+    Topology t; Shape sh;
+    if (const char *e = describe(d[s], s ? &top : nullptr, t, sh)) return num_shapes > 1 ? "shape " + std::to_string(s) + ": " + e : std::string(e);
+    if (s && !same_topology(t, top)) return "shape " + std::to_string(s) + " differs from shape 0 in more than its geometry";
+    append_shape(t, sh, num_shapes > 1, out);
+    if (s == 0) { top = std::move(t); first = std::move(sh); }
+  }
+  const Tree &tree = top.tree;
+  Hdr &h = out.h = top.h;
+  h.nlev = tree.nlev; h.maxlev = tree.maxlev; h.n_sumsmall = (int)tree.sum_small.size(); h.n_sumbig = (int)tree.sum_big.size();
+  out.hc = tree.hc; out.candb = top.candb; out.illegal_mask = top.illegal_mask; out.meaninertia = first.meaninertia;
+  const bool alias = h.nb > 32 && alias_layout_fits(h.nb, h.maxlev, h.nslot) && !plain_layout;
+  out.shared = assemble_blob(top, num_shapes == 1 ? &first : nullptr, alias, h, out.hc);
+  if (const char *e = lds_layouts(alias, out)) return e;
+  body_contact_tables(top, out);
+  return "";
 }
 
 inline int obs_size(const Hdr &h, const ss_env_cfg &c) {

@@ -1,7 +1,8 @@
 // host_paths_check.cpp — the host side of the C ABI (smplsim_amd/csrc/ss_api.h) on a backend without a device, for a
 // run under AddressSanitizer / UBSan (tests/test_host_paths_sanitized.py builds and runs it): model and batch creation, every
-// setter, a refused and an accepted ss_imitation_bind, teardown — once with every allocation and upload succeeding, then again
-// with the n-th one failing, for every n until a run makes no failing call.  Any leak, double free or undefined behaviour on one
+// setter, a refused and an accepted ss_imitation_bind, a model of three body shapes, teardown — once with every allocation and upload
+// succeeding, then again with the n-th one failing, for every n until a run makes no failing call; before that, every description that
+// model creation refuses.  Any leak, double free or undefined behaviour on one
 // of these paths ends the program with the sanitizer's report.  usage: host_paths_check MJCF_FILE
 #include <cstdio>
 #include <cstdlib>
@@ -115,6 +116,35 @@ void run(const std::string &xml, const ss_model_desc *descs) {
     } else if (b) die("ss_batch_create failed and handed a batch out");
     ss_model_destroy(m2);
   } else if (m2) die("ss_model_create_shapes failed and handed a model out");
+
+  // three body shapes: per-shape tables concatenated, six tables uploaded
+  ss_model *m3 = nullptr;
+  if (went(ss_model_create_shapes(descs, 3, 0, &m3), "ss_model_create_shapes (3 shapes)")) ss_model_destroy(m3);
+  else if (m3) die("ss_model_create_shapes failed and handed a model out");
+}
+
+// every description that model creation refuses: one change to a good description at a time, the code and the message, nothing handed out
+void refusals(ss::mjcf::Compiled *c, ss_model_desc *d) {      // d[i]: a copy of c[i].desc, its arrays are c[i]'s
+  auto refused = [&](int num_shapes, const char *msg) {
+    ss_model *m = nullptr;
+    const int rc = num_shapes == 1 ? ss_model_create(d, 0, &m) : ss_model_create_shapes(d, num_shapes, 0, &m);
+    if (rc != SS_ERR_INVALID || m || strcmp(ss_last_error(), msg)) { fprintf(stderr, "expected the refusal \"%s\"\n", msg); die("a refusal went wrong"); }
+  };
+  auto with = [&](auto &slot, auto value, int num_shapes, const char *msg) { const auto old = slot; slot = value; refused(num_shapes, msg); slot = old; };
+  with(d->nbody, 0, 1, "nbody must be in [1,63]");
+  with(c[0].parent[0], 0, 1, "body 0 must be the root");
+  with(c[0].parent[1], 1, 1, "parents must precede children");
+  with(c[0].parent[9], 1, 1, "bodies must be in depth-first order");          // body 8 is the end of the right leg: 1 is none of its ancestors
+  with(c[0].arm[2], 0.01, 1, "armature on the free joint is not supported");
+  with(c[0].adof[0], 5, 1, "bad actuator_dof");
+  with(c[0].gtype[3], 5, 1, "unknown geom type");
+  with(d->impratio, 2.0, 1, "impratio != 1 is not supported");
+  with(c[1].kp[3], 2 * c[1].kp[3], 2, "shape 1 differs from shape 0 in more than its geometry");
+  with(d[2].impratio, 2.0, 3, "shape 2: impratio != 1 is not supported");
+  const std::vector<int32_t> parents = c[0].parent;         // a star: every rooting has a level of more than 16 bodies
+  std::fill(c[0].parent.begin() + 1, c[0].parent.end(), 0);
+  refused(1, "more than 16 nodes in one tree level");
+  std::copy(parents.begin(), parents.end(), c[0].parent.begin());
 }
 
 }  // namespace
@@ -125,9 +155,15 @@ int main(int argc, char **argv) {
   text << std::ifstream(argv[1]).rdbuf();
   const std::string xml = text.str();
   if (xml.empty()) { fprintf(stderr, "host_paths_check: cannot read %s\n", argv[1]); return 2; }
-  ss::mjcf::Compiled c[2]; std::string e;                    // the two body shapes of ss_model_create_shapes: the same one twice
+  ss::mjcf::Compiled c[3]; std::string e;                    // the body shapes of ss_model_create_shapes: geom sizes and body offsets scaled
   for (auto &ci : c) if (!ss::mjcf::compile(xml.data(), xml.size(), nullptr, ci, e)) die(e.c_str());
-  const ss_model_desc descs[2] = {c[0].desc, c[1].desc};
+  for (double &x : c[1].gsize) x *= 0.9;
+  for (double &x : c[1].pos) x *= 0.9;
+  for (double &x : c[2].gsize) x *= 1.1;
+  for (double &x : c[2].pos) x *= 1.1;
+  ss_model_desc descs[3] = {c[0].desc, c[1].desc, c[2].desc};
+  refusals(c, descs);
+  FakeBackend::calls = 0;
   run(xml, descs);                                           // nothing fails
   if (FakeBackend::failed) die("a failure without one injected");
   const long total = FakeBackend::calls;

@@ -403,5 +403,49 @@ extern "C" void ss_emu_launch_geometry(int nenv, int cus, int envs_per_wg, int f
   out[0] = g.wgs; out[1] = g.envs_per_wg; out[2] = (long)g.lds_bytes;
 }
 
+// test hook: what model creation made (tests/test_host_tables_cpu.py), one 64-bit FNV-1a digest per item, out[13]: the six uploaded
+// tables (shared, bodyc, candc, candb, pairs + sctab, geomc) read back through the backend, then h, h_sc, hc and sc field by field (no
+// padding bytes), illegal_mask, meaninertia and the text of self_collision_unavailable
+namespace {
+struct Fnv {
+  uint64_t v = 14695981039346656037ull;
+  void bytes(const void *p, size_t n) { for (size_t i = 0; i < n; i++) v = (v ^ static_cast<const unsigned char *>(p)[i]) * 1099511628211ull; }
+  template <class... T> Fnv &fields(const T &...x) { (bytes(&x, sizeof x), ...); return *this; }
+};
+template <class T> uint64_t table_digest(const T *dev, size_t n) {
+  std::vector<T> host(n);
+  EmuBackend::download(host.data(), dev, n * sizeof(T));
+  Fnv f; f.bytes(host.data(), n * sizeof(T));
+  return f.v;
+}
+uint64_t hdr_digest(const ss::Hdr &h) {
+  return Fnv().fields(h.nb, h.nn, h.nv, h.nq, h.nu, h.ncand, h.nlev, h.a_stride, h.nbox, h.nslot, h.maxlev, h.l_Rloc, h.l_w2, h.arm_lean,
+                      h.o_dofc, h.o_boff, h.o_chainnode, h.o_ndepth, h.l_act, h.o_bparent, h.o_sumsmall, h.o_sumbig, h.o_sumcover, h.n_sumsmall, h.n_sumbig, h.shared_words,
+                      h.l_q, h.l_v, h.l_a, h.l_tau, h.l_Fb, h.l_Pb, h.l_delta, h.l_diag, h.l_S, h.l_Ab, h.l_An, h.l_Aown, h.l_IA, h.l_Ubuf, h.l_Wst,
+                      h.l_R, h.l_r, h.l_Gb, h.l_tmp, h.l_V, h.l_Iown, h.ia_stride, h.env_floats, h.dt, h.grav, h.margin, h.mu, h.solimp, h.K, h.B, h.qpos0_root).v;
+}
+}  // namespace
+extern "C" void ss_emu_model_digests(const ss_model *m, uint64_t *out) {
+  const ss::HostModel &hm = m->hm;
+  const ss::Hdr &h = hm.h;
+  const size_t S = (size_t)m->num_shapes;
+  out[0] = table_digest(m->d_shared, hm.shared.size());
+  out[1] = table_digest(m->d_bodyc, S == 1 ? (size_t)h.nb * ss::kBodyC : S * ss::shape_stride(h));   // several shapes: each block ends in its dof inverse weights
+  out[2] = table_digest(m->d_candc, S * h.ncand * ss::kCandC);
+  out[3] = table_digest(m->d_candb, (size_t)h.ncand);
+  out[4] = table_digest(m->d_pairs, S * 2 * hm.sc.npair + 3 * (size_t)h.nb);
+  out[5] = table_digest(m->d_geomc, S * h.nb * ss::kGeomC);
+  out[6] = hdr_digest(h);
+  out[7] = hdr_digest(hm.h_sc);
+  const ss::HdrC &c = hm.hc;
+  out[8] = Fnv().fields(c.nlev, c.o_lev, c.root, c.pel_level, c.nkpack, c.cpack, c.chain, c.neg).v;
+  const ss::HdrSC &s = hm.sc;
+  out[9] = Fnv().fields(s.npair, s.l_H, s.l_g, s.l_list, s.l_Wst2, s.hloc, s.o_sctab, s.l_gc, s.l_tab, s.nmax, s.l_cand, s.l_zb, s.env_floats).v;
+  out[10] = Fnv().fields(hm.illegal_mask).v;
+  out[11] = Fnv().fields(hm.meaninertia).v;
+  Fnv t; t.bytes(hm.self_collision_unavailable.data(), hm.self_collision_unavailable.size());
+  out[12] = t.v;
+}
+
 SS_DEFINE_C_API(EmuBackend)
 SS_DEFINE_MOTION_API(EmuBackend)
