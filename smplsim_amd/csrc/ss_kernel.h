@@ -241,6 +241,17 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
   // are then recomputed per stage (a few VALU ops) instead of being hoisted out of the state machine and
   // spilled to scratch for the whole launch
   SS_DEV void fresh() { lane = w->opaque_v(lane); }
+  // `early` (the result of an LDS read that is needed later) is in its register where `b` (one that is needed here) is: the compiler
+  // issues the read of `early` no later than this and waits for both at once, instead of sinking it to its first use.  A scheduling
+  // hint of the device build, nothing elsewhere.
+  SS_DEV static real arrived(int &early, real b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(early), "+v"(b));
+#else
+    (void)early;
+#endif
+    return b;
+  }
   // constraint registers are rebuilt by make_constraints() of the same pass; clearing them at the top of a pass ends
   // their live ranges there, so they do not occupy VGPRs (or scratch) across forward_kin
   SS_DEV void drop_constraints() {
@@ -999,6 +1010,9 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
   // 6 / 7 levels): level bounds and record offsets become immediates (+3 % on the SMPL headline, same bits —
   // profiles/r03_centred_elimination.md 16); with a runtime tree they stay loops.
   static constexpr int kUnrollLevels = HT::fixed ? 16 : 1;
+  // Records requested a level ahead (aba_solve) in the unrolled sweeps only: with a runtime tree the word lives across the loop's
+  // back edge, and 8 of those 15 instantiations paid for it with 4 to 24 bytes more scratch per lane
+  static constexpr bool kAhead = HT::fixed;
   SS_DEV static void st4w(real *p, real a, real b, real c, real d) { float4_t v; v.x = a; v.y = b; v.z = c; v.w = d; *reinterpret_cast<float4_t *>(p) = v; }
 
   SS_DEV void write_own_inertia() {                          // Aown[b] = expand(Ib), packed upper triangle (ang;lin)
@@ -1061,6 +1075,42 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
       if constexpr (HT::fixed) return L >= 1 && L < hc.nlev && ((hc.chain >> (L - 1)) & 1ull);
       else return false;
     };
+    // A level's record (word 0: body, joint, neighbour, flags) only forms the addresses of the level's first data reads, and its own
+    // address depends on the lane and the tree alone: it is requested BEFORE the hand-off that precedes the level — level L asks for
+    // the record of the level that runs next, with that level's own width and clamp — so that a level's entry waits for one LDS round
+    // trip, the data's, not for two.  Left alone the compiler sinks such a read to its first use behind the hand-off, and pinned just
+    // before the hand-off it waits there instead: arrived() ties the word to data the running level waits for anyway, so the read is
+    // issued with that level's first reads and its round trip hides behind theirs.
+    // ((W, y) rows kept by record index instead of by body, so that the W row's address needs no record at all, measured 0.3 % SLOWER
+    // on top of this: profiles/sweep_prefetch_ab.txt.  With the record there at the level's entry the address costs nothing.)
+    int rec0[NPASS], recn[NPASS];                            // word 0 of the records of the level that runs / that runs next
+    auto request_records = [&](int s0n, int nkn) {           // a level of nkn nodes whose records start at s0n
+      if constexpr (!kAhead) return;
+#pragma unroll
+      for (int ps = 0; ps < NPASS; ps++) {
+        if (ps > 0 && ps * 8 >= nkn) continue;
+        const int kn = ps * 8 + g < nkn - 1 ? ps * 8 + g : nkn - 1;
+        recn[ps] = ti(hc.o_lev, 2 * (s0n + kn));
+      }
+    };
+    auto records_with = [&](int nkn, real with) -> real {    // the requested words are there when `with` is
+      if constexpr (!kAhead) return with;
+#pragma unroll
+      for (int ps = 0; ps < NPASS; ps++) {
+        if (ps > 0 && ps * 8 >= nkn) continue;
+        with = arrived(recn[ps], with);
+      }
+      return with;
+    };
+    auto last_pass = [&](int nk_) { return (nk_ - 1) / 8 < NPASS - 1 ? (nk_ - 1) / 8 : NPASS - 1; };   // of a level of nk_ nodes
+    auto next_level = [&]() {
+      if constexpr (!kAhead) return;
+#pragma unroll
+      for (int ps = 0; ps < NPASS; ps++) rec0[ps] = recn[ps];
+    };
+#pragma unroll
+    for (int ps = 0; ps < NPASS; ps++) rec0[ps] = recn[ps] = 0;
+    if (hc.nlev >= 1) { request_records(s0 - NKC(hc.nlev), NKC(hc.nlev)); next_level(); }
 #pragma unroll kUnrollLevels
     for (int L = hc.nlev; L >= 1; --L) {
       const int nk = NKC(L);
@@ -1078,7 +1128,7 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
         const int kk = ps * 8 + g < nk - 1 ? ps * 8 + g : nk - 1;
         stores[ps] = has_row && ps * 8 + g < nk;
         {
-          const int e0 = ti(hc.o_lev, 2 * (s0 + kk)), e1 = ti(hc.o_lev, 2 * (s0 + kk) + 1);
+          const int e0 = kAhead ? rec0[ps] : ti(hc.o_lev, 2 * (s0 + kk)), e1 = ti(hc.o_lev, 2 * (s0 + kk) + 1);
           const int b = e0 & 255, jn = (e0 >> 8) & 255, cfirst = e1 & 255, cc = (e1 >> 8) & 255;
           // (a constant of the unrolled level: only the levels between the tree's root and the kinematic root hold negated joints)
           const bool lev_neg = !HT::fixed || L > 32 || ((hc.neg >> (L - 1)) & 1ull);
@@ -1155,6 +1205,7 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
 #pragma unroll
         for (int t = 0; t < 9; t++) red[ps][t] = w->sum8(red[ps][t]);
       }
+      if (L > 1) request_records(s0 - NKC(L - 1), NKC(L - 1));   // the next level's, with this part's U rows
 #pragma unroll
       for (int ps = 0; ps < NPASS; ps++) {                    // ---- part 2: joint-space 3x3 algebra, rows handed towards the root
         if (ps > 0 && ps * 8 >= nk) continue;
@@ -1163,12 +1214,16 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
           float4_t U[6];
 #pragma unroll
           for (int c = 0; c < 6; c++) U[c] = ld4(Ubuf + (kk * 6 + c) * 4);
+          // (this part's reads all stand before the tie: the compiler moves no LDS access across it)
+          const real xj0 = x[3 * jn], xj1 = x[3 * jn + 1], xj2 = x[3 * jn + 2], dg1 = diag[3 * jn + 1], dg2 = diag[3 * jn + 2];
+          real dg0 = diag[3 * jn];
+          if (L > 1 && ps == last_pass(nk)) dg0 = records_with(NKC(L - 1), dg0);
           // with S' = sgn S_j:  D, IA' = IA - W U^T and W U^T do not see the sign; u' = sgn u = sgn b_j - S_j^T pA gives y' = sgn y,
           // pA' = pA + U y' and, on the way back, z = sgn q''_j = y' - W^T a_e, a_b = a_e + S_j z: W and y' are stored for the unsigned S_j
           const real sgn = sg[ps];
-          const real u0 = sgn * x[3 * jn] - red[ps][6], u1 = sgn * x[3 * jn + 1] - red[ps][7], u2 = sgn * x[3 * jn + 2] - red[ps][8];
+          const real u0 = sgn * xj0 - red[ps][6], u1 = sgn * xj1 - red[ps][7], u2 = sgn * xj2 - red[ps][8];
           Ldl3 Dj;
-          Dj.factor(red[ps][0] + diag[3 * jn], red[ps][1], red[ps][2] + diag[3 * jn + 1], red[ps][3], red[ps][4], red[ps][5] + diag[3 * jn + 2]);
+          Dj.factor(red[ps][0] + dg0, red[ps][1], red[ps][2] + dg1, red[ps][3], red[ps][4], red[ps][5] + dg2);
           real y0, y1, y2, w0, w1, w2;
           Dj.solve(u0, u1, u2, y0, y1, y2);
           const real a0 = Ur[ps][0], a1 = Ur[ps][1], a2 = Ur[ps][2];
@@ -1201,6 +1256,7 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
           }
         }
       }
+      if (L > 1) next_level();
       SS_FTICK(PF_F_P2);
       w->sync();
     }
@@ -1224,16 +1280,20 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
       }
       bool dense = false;
       if constexpr (SELFCOL) dense = cmask != 0ull;
-      if (dense) dense_solve(cmask, x, rw, pv);               // the root's six unknowns are part of the dense system of the coupled joints
-      else {
+      if (dense) {
+        dense_solve(cmask, x, rw, pv);                        // the root's six unknowns are part of the dense system of the coupled joints
+        if (hc.nlev >= 1) { request_records(0, NKC(1)); records_with(NKC(1), real(0)); }
+      } else {
       if (lane < 6) { st4w(rows + 8 * lane, rw[0], rw[1], rw[2], rw[3]); st4w(rows + 8 * lane + 4, rw[4], rw[5], -pv, 0.f); }
       w->sync();
       real A6[6][6], f6[6];                                   // every lane solves the same 6x6 system
+      if (hc.nlev >= 1) request_records(0, NKC(1));           // level 1's, for the sweep away from the root: with the system's rows
 #pragma unroll
       for (int i = 0; i < 6; i++) {
         const float4_t v0 = ld4(rows + 8 * i), v1 = ld4(rows + 8 * i + 4);
         A6[i][0] = v0.x; A6[i][1] = v0.y; A6[i][2] = v0.z; A6[i][3] = v0.w; A6[i][4] = v1.x; A6[i][5] = v1.y; f6[i] = v1.z;
       }
+      if (hc.nlev >= 1) A6[0][0] = records_with(NKC(1), A6[0][0]);
 #ifndef SS_ROOT_BLOCKS
       // L D L^T of the 6x6 (symmetric positive definite: no pivoting needed), unrolled into registers: 65 multiply-adds and six
       // reciprocals for the factors, 36 for the two substitutions (rounds 1-3: elimination by 3x3 blocks with closed-form inverses,
@@ -1323,11 +1383,13 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
     real accp[NPASS];                                        // along a 1:1 stretch the neighbour's acceleration is this lane's own of the level before
 #pragma unroll
     for (int ps = 0; ps < NPASS; ps++) accp[ps] = 0.f;
+    next_level();
 #pragma unroll kUnrollLevels
     for (int L = 1; L <= hc.nlev; L++) {
       const int nk = NKC(L);
       const bool pel_level = L == hc.pel_level;               // wave-uniform: this level holds body 0
       const bool chain_dn = chain_level(L - 1);
+      if (L < hc.nlev) request_records(s0 + nk, NKC(L + 1));   // the next level's, with this level's first W row
 #pragma unroll
       for (int ps = 0; ps < NPASS; ps++) {
         if (ps > 0 && ps * 8 >= nk) continue;
@@ -1335,14 +1397,15 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
         //  and the inputs of the group sums is guarded)
         const int kk = ps * 8 + g < nk - 1 ? ps * 8 + g : nk - 1;
         const bool stores = has_row && ps * 8 + g < nk;
-        const int e0 = ti(hc.o_lev, 2 * (s0 + kk)), en = (e0 >> 16) & 255;
+        const int e0 = kAhead ? rec0[ps] : ti(hc.o_lev, 2 * (s0 + kk)), en = (e0 >> 16) & 255;
         const int b = e0 & 255, jn = (e0 >> 8) & 255, pel = (e0 >> 25) & 1;
         const bool lev_neg = !HT::fixed || L > 32 || ((hc.neg >> (L - 1)) & 1ull);
         const real sgn = (lev_neg && ((e0 >> 24) & 1)) ? real(-1) : real(1);
-        const float4_t wr = ld4(Wst + (b * 6 + rr) * 4);
+        float4_t wr = ld4(Wst + (b * 6 + rr) * 4);
         const real *sn = S + 18 * jn + rr;
         const real s_0 = sn[0], s_1 = sn[6], s_2 = sn[12], nsg = -sgn;
         const real apr = chain_dn ? accp[ps] : An[8 * (en + 1) + rr];
+        if (L < hc.nlev && ps == last_pass(nk)) wr.x = records_with(NKC(L + 1), wr.x);   // (behind the level's reads: the compiler moves no LDS access across the tie)
         real p0 = wr.x * apr - (rr == 0 ? wr.w : 0.f), p1 = wr.y * apr - (rr == 1 ? wr.w : 0.f), p2 = wr.z * apr - (rr == 2 ? wr.w : 0.f);
         p0 = has_row ? p0 : 0.f; p1 = has_row ? p1 : 0.f; p2 = has_row ? p2 : 0.f;   // the sum is the one over the six rows
         p0 = w->sum8(p0); p1 = w->sum8(p1); p2 = w->sum8(p2);   // = -z = -sgn q''_j in every lane of the group
@@ -1366,6 +1429,7 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
         }
       }
       s0 += nk;
+      if (L < hc.nlev) next_level();
       w->sync();
     }
     SS_FTICK(PF_F_BSOL);
