@@ -71,17 +71,17 @@ __global__ void __launch_bounds__(MAXT) ss_env_kernel(const ss::KArgs k) {
     int mode = k.mode;
     if constexpr (IMIT) {
       const ss::mo::ImFused *f = static_cast<const ss::mo::ImFused *>(k.im);
-      ss::run_env<WaveGpu, DOFP, CANDP, SLOTP, NPASS, BODYOUT, SHAPED, HT, SELFCOL>(&w, &k, lds, L, env, mode, pool);
+      ss::run_env<WaveGpu, DOFP, CANDP, SLOTP, NPASS, BODYOUT, SHAPED, HT, SELFCOL, IMIT>(&w, &k, lds, L, env, mode, pool);
       w.sync();
       if (ss::mo::fused_after_step(&w, f, k.im_rand, env)) {
-        ss::run_env<WaveGpu, DOFP, CANDP, SLOTP, NPASS, BODYOUT, SHAPED, HT, SELFCOL>(&w, &k, lds, L, env, ss::MODE_RESET, pool);
+        ss::run_env<WaveGpu, DOFP, CANDP, SLOTP, NPASS, BODYOUT, SHAPED, HT, SELFCOL, IMIT>(&w, &k, lds, L, env, ss::MODE_RESET, pool);
         w.sync();
         ss::mo::fused_after_reset(&w, f, env);
       }
       continue;
     }
     for (int rep = 0; rep < 2; rep++) {                       // second trip = fused Default reset of an env whose episode ended
-      const bool again = ss::run_env<WaveGpu, DOFP, CANDP, SLOTP, NPASS, BODYOUT, SHAPED, HT, SELFCOL>(&w, &k, lds, L, env, mode, pool);
+      const bool again = ss::run_env<WaveGpu, DOFP, CANDP, SLOTP, NPASS, BODYOUT, SHAPED, HT, SELFCOL, IMIT>(&w, &k, lds, L, env, mode, pool);
       w.sync();
       if (!again) break;
       mode = ss::MODE_RESET;

@@ -142,7 +142,7 @@ template <> struct SelfColState<true> {
 template <bool MAYBE_LEAN> struct LeanState { const real *act_g = nullptr; SS_DEV const real *action_ptr() const { return act_g; } SS_DEV void set_action_ptr(const real *p) { act_g = p; } };
 template <> struct LeanState<false> { SS_DEV const real *action_ptr() const { return nullptr; } SS_DEV void set_action_ptr(const real *) {} };
 
-template <class W, int DOFP, int CANDP, int SLOTP, int NPASS, bool SHAPED = false, class HT = HdrRuntime, bool SELFCOL = false>
+template <class W, int DOFP, int CANDP, int SLOTP, int NPASS, bool SHAPED = false, class HT = HdrRuntime, bool SELFCOL = false, bool IMIT = false>
 struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lean> {
   W *w;
   const KArgs *k;
@@ -965,29 +965,45 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
     }
   }
 
-  // rows: jar (from A = Ab, x = a) or jd (from A = Ad, x = delta)
+  // this lane's dofs of a joint-space vector, one per dof pass; a lane without a dof in a pass reads the last dof (a valid
+  // address: nothing of it reaches a result, the callers select it away), so the reads need no branch and issue together
+  SS_DEV int dof_clamped(int p) const { const int i = p * 64 + lane, nv = hdr().nv; return i < nv ? i : nv - 1; }
+  SS_DEV void dof_values(const real *x, real (&o)[DOFP]) const {
+#pragma unroll
+    for (int p = 0; p < DOFP; p++) o[p] = x[dof_clamped(p)];
+  }
+
+  // rows: jar (from A = Ab, x = a) or jd (from A = Ad, x = delta); x: this lane's dofs (dof_values)
   // A: spatial accelerations, body b at A + stride * b
-  SS_DEV void eval_rows(const real *A, int stride, const real *x, bool is_delta) {
+  // Straight-line code: a lane without a contact reads body 0 and a dof without a limit row keeps what it has, both by selects
+  SS_DEV void eval_rows(const real *A, int stride, const real (&x)[DOFP], bool is_delta) {
     eval_self_rows(A, stride, is_delta);
     const real mu = k->h.mu;
 #pragma unroll
     for (int p = 0; p < SLOTP; p++) {
       Contact &c = con[p];
-      if (!c.active) continue;
-      const real *Ab_ = A + stride * c.body;
-      real ax = Ab_[3] + Ab_[1] * c.rz - Ab_[2] * c.ry;
-      real ay = Ab_[4] + Ab_[2] * c.rx - Ab_[0] * c.rz;
-      real az = Ab_[5] + Ab_[0] * c.ry - Ab_[1] * c.rx;
+      const bool act = c.active != 0;
+      if constexpr (kRowBranches) { if (!act) continue; }
+      const real *Ab_ = A + stride * (act ? c.body : 0);
+      const real A0 = Ab_[0], A1 = Ab_[1], A2 = Ab_[2], A3 = Ab_[3], A4 = Ab_[4], A5 = Ab_[5];
+      real ax = A3 + A1 * c.rz - A2 * c.ry;
+      real ay = A4 + A2 * c.rx - A0 * c.rz;
+      real az = A5 + A0 * c.ry - A1 * c.rx;
       real t1 = mu * (c.t1x * ax + c.t1y * ay), t2 = mu * (-c.t1y * ax + c.t1x * ay);
-      if (is_delta) { c.jd[0] = az + t1; c.jd[1] = az - t1; c.jd[2] = az + t2; c.jd[3] = az - t2; }
-      else { c.jar[0] = az + t1 - c.aref[0]; c.jar[1] = az - t1 - c.aref[1]; c.jar[2] = az + t2 - c.aref[2]; c.jar[3] = az - t2 - c.aref[3]; }
+      if (is_delta) {
+        const real d0 = az + t1, d1 = az - t1, d2 = az + t2, d3 = az - t2;
+        c.jd[0] = act ? d0 : c.jd[0]; c.jd[1] = act ? d1 : c.jd[1]; c.jd[2] = act ? d2 : c.jd[2]; c.jd[3] = act ? d3 : c.jd[3];
+      } else {
+        const real j0 = az + t1 - c.aref[0], j1 = az - t1 - c.aref[1], j2 = az + t2 - c.aref[2], j3 = az - t2 - c.aref[3];
+        c.jar[0] = act ? j0 : c.jar[0]; c.jar[1] = act ? j1 : c.jar[1]; c.jar[2] = act ? j2 : c.jar[2]; c.jar[3] = act ? j3 : c.jar[3];
+      }
     }
 #pragma unroll
     for (int p = 0; p < DOFP; p++) {
-      int i = p * 64 + lane;
       Limit &l = lim[p];
-      if (l.sign == 0.f) continue;
-      if (is_delta) l.jd = l.sign * x[i]; else l.jar = l.sign * x[i] - l.aref;
+      const bool has = l.sign != 0.f;
+      if (is_delta) { const real d = l.sign * x[p]; l.jd = has ? d : l.jd; }
+      else { const real j = l.sign * x[p] - l.aref; l.jar = has ? j : l.jar; }
     }
   }
 
@@ -1013,6 +1029,10 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
   // Records requested a level ahead (aba_solve) in the unrolled sweeps only: with a runtime tree the word lives across the loop's
   // back edge, and 8 of those 15 instantiations paid for it with 4 to 24 bytes more scratch per lane
   static constexpr bool kAhead = HT::fixed;
+  // Branches around the contact rows of eval_rows and inside row_dcost, as before the row code became straight-line code, in the
+  // imitation unit's fixed-layout kernel only (IMIT: the kernel's own parameter, handed down by run_env): without them that one
+  // instantiation pays 20 bytes more scratch per lane (profiles/newton_rows_counts.txt); same values either way
+  static constexpr bool kRowBranches = IMIT && HT::fixed;
   SS_DEV static void st4w(real *p, real a, real b, real c, real d) { float4_t v; v.x = a; v.y = b; v.z = c; v.w = d; *reinterpret_cast<float4_t *>(p) = v; }
 
   SS_DEV void write_own_inertia() {                          // Aown[b] = expand(Ib), packed upper triangle (ang;lin)
@@ -1933,10 +1953,11 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
     }
 #pragma unroll
     for (int p = 0; p < DOFP; p++) {
-      const Limit &l = lim[p];
-      if (l.sign == 0.f) continue;
-      real x = l.jar + al * l.jd;
-      if (x < 0.f) { s1 += l.D * x * l.jd; s2 += l.D * l.jd * l.jd; }
+      const Limit &l = lim[p];                               // (a dof without a limit row: selected away, no branch)
+      const real x = l.jar + al * l.jd;
+      const bool on = l.sign != 0.f && x < 0.f;
+      const real t1 = s1 + l.D * x * l.jd, t2 = s2 + l.D * l.jd * l.jd;
+      s1 = on ? t1 : s1; s2 = on ? t2 : s2;
     }
     self_ls_terms(al, s1, s2);
     d1 = c1 + al * c2 + w->sum(s1);
@@ -1947,7 +1968,9 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
   // between newton_prepare() and newton_finish() in the driver's solver loop.
   SS_DEV void newton_begin() {
     fresh();
-    eval_rows(Ab, 6, a, false);                              // Ab = J_b a was left by forward_kin's chain sums
+    real xa[DOFP];
+    dof_values(a, xa);
+    eval_rows(Ab, 6, xa, false);                             // Ab = J_b a was left by forward_kin's chain sums
   }
 
   // right-hand side of the Newton system in two parts — joint space (-> delta) and per-body forces Pb —, diagonal terms
@@ -2101,23 +2124,39 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
   SS_DEV bool newton_finish() {
     fresh();
     typename HT::type h = HT::view(k->h);
-    eval_rows(An + 8, 8, delta, true);                       // aba_solve left the body accelerations of delta in An
+    // Everything the sums below read from LDS is requested here, in one batch with the contact rows' reads of eval_rows: no read
+    // depends on another one's result.  A lane without a dof or a body reads a clamped index and its terms are selected away
+    // (the accumulated value is selected, not an added zero: -0 + +0 is not -0).
+    real xa[DOFP], xt[DOFP], xd[DOFP], xm[DOFP], ab_[6], pb_[6];
+    dof_values(a, xa); dof_values(tau, xt); dof_values(delta, xd);
+#pragma unroll
+    for (int p = 0; p < DOFP; p++) xm[p] = armature(dof_clamped(p));
+    {
+      const int lb = lane < h.nb ? lane : h.nb - 1;
+#pragma unroll
+      for (int c = 0; c < 6; c++) { ab_[c] = An[8 * (lb + 1) + c]; pb_[c] = Pb[6 * lb + c]; }
+    }
+    eval_rows(An + 8, 8, xd, true);                          // aba_solve left the body accelerations of delta in An
     real dg_ = 0.f, dgabs = 0.f, s_a = 0.f, s_b = 0.f;
 #pragma unroll
     for (int p = 0; p < DOFP; p++) {                          // delta . gradient, joint-space part (same terms as newton_prepare)
-      int i = p * 64 + lane;
-      if (i < h.nv) {
-        real s_ = armature(i) * a[i] - tau[i];
-        const Limit &l = lim[p];
-        if (l.sign != 0.f && l.jar < 0.f) s_ += l.sign * l.D * l.jar;
-        const real t_ = delta[i] * s_;
-        dg_ += t_; dgabs += SS_M(fabs)(t_);
-      }
+      const bool has = p * 64 + lane < h.nv;
+      real s_ = xm[p] * xa[p] - xt[p];
+      const Limit &l = lim[p];
+      const real sl = s_ + l.sign * l.D * l.jar;
+      s_ = l.sign != 0.f && l.jar < 0.f ? sl : s_;
+      const real t_ = xd[p] * s_;
+      const real dn = dg_ + t_, da = dgabs + SS_M(fabs)(t_);
+      dg_ = has ? dn : dg_; dgabs = has ? da : dgabs;
     }
-    if (lane < h.nb) {                                        // body part: (J_b delta) . Pb_b
-      const real *ab_ = An + 8 * (lane + 1), *pb_ = Pb + 6 * lane;
+    {                                                         // body part: (J_b delta) . Pb_b
+      const bool has = lane < h.nb;
 #pragma unroll
-      for (int c = 0; c < 6; c++) { const real t_ = ab_[c] * pb_[c]; dg_ += t_; dgabs += SS_M(fabs)(t_); }
+      for (int c = 0; c < 6; c++) {
+        const real t_ = ab_[c] * pb_[c];
+        const real dn = dg_ + t_, da = dgabs + SS_M(fabs)(t_);
+        dg_ = has ? dn : dg_; dgabs = has ? da : dgabs;
+      }
     }
 #pragma unroll
     for (int p = 0; p < SLOTP; p++) {
@@ -2129,7 +2168,9 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
 #pragma unroll
     for (int p = 0; p < DOFP; p++) {
       const Limit &l = lim[p];
-      if (l.sign != 0.f && l.jar < 0.f) { s_a += l.D * l.jar * l.jd; s_b += l.D * l.jd * l.jd; }
+      const bool on = l.sign != 0.f && l.jar < 0.f;
+      const real ta = s_a + l.D * l.jar * l.jd, tb = s_b + l.D * l.jd * l.jd;
+      s_a = on ? ta : s_a; s_b = on ? tb : s_b;
     }
     // body-body rows (SELFCOL): their forces are part of Pb (newton_prepare), so dg_ holds their share of delta . gradient already
     if constexpr (SELFCOL) {
@@ -2196,11 +2237,12 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
 #pragma unroll
     for (int p = 0; p < DOFP; p++) {
       Limit &l = lim[p];
-      if (l.sign == 0.f) continue;
+      const bool has = l.sign != 0.f;
       const real x0 = l.jar, st_ = al * l.jd, nj = x0 + st_;
-      changed |= (nj < 0.f) != (x0 < 0.f);
-      dcost += l.D * row_dcost(x0, st_, nj);
-      l.jar = nj;
+      const real dc_ = dcost + l.D * row_dcost(x0, st_, nj);
+      changed |= has && (nj < 0.f) != (x0 < 0.f);
+      dcost = has ? dc_ : dcost;
+      l.jar = has ? nj : x0;
     }
     if constexpr (SELFCOL) {
       if (lane < this->nself) {
@@ -2225,8 +2267,11 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
   }
   // one row's term of the cost change along the line, times 2 / D:  (x1)_-^2 - (x0)_-^2  with x1 = x0 + st
   SS_DEV static real row_dcost(real x0, real st, real x1) {
+    // (the three candidates first, then two selects: straight-line code, no branch per row)
     const bool a0 = x0 < 0.f, a1 = x1 < 0.f;
-    return a0 ? (a1 ? st * (x0 + x1) : -x0 * x0) : (a1 ? x1 * x1 : real(0));
+    if constexpr (kRowBranches) return a0 ? (a1 ? st * (x0 + x1) : -x0 * x0) : (a1 ? x1 * x1 : real(0));
+    const real both = st * (x0 + x1), off = -x0 * x0, on = x1 * x1;
+    return a0 ? (a1 ? both : off) : (a1 ? on : real(0));
   }
 
   // ------------------------------------------------------------------ controllers (torque for the NEXT mj_step)
@@ -2469,14 +2514,14 @@ enum { SOLVE_NEWTON = 1, SOLVE_SPD = 2 };
 // BODYOUT: the instantiation whose step / reset passes also write the body frames (ss_set_body_outputs).  A separate
 // instantiation because the extra epilogue costs the headline step kernel 3.7% (register allocation of the hot loops
 // shifts) even when the pointer is null — callers that do not ask for it keep the plain one.
-template <class W, int DOFP, int CANDP, int SLOTP, int NPASS, bool BODYOUT = false, bool SHAPED = false, class HT = HdrRuntime, bool SELFCOL = false>
+template <class W, int DOFP, int CANDP, int SLOTP, int NPASS, bool BODYOUT = false, bool SHAPED = false, class HT = HdrRuntime, bool SELFCOL = false, bool IMIT = false>
 SS_DEV bool run_env(W *w, const KArgs *k, const uint32_t *T, real *L, int env, int mode, real *pool = nullptr) {
   typename HT::type h = HT::view(k->h);
   const ss_env_cfg &cf = k->cfg;
   const ss_state &st = k->st;
   const bool fused_pass = mode != k->mode;                    // the in-launch reset of an env that just finished
   if (!fused_pass && k->mask && !k->mask[env]) return false;
-  Sim<W, DOFP, CANDP, SLOTP, NPASS, SHAPED, HT, SELFCOL> sim;
+  Sim<W, DOFP, CANDP, SLOTP, NPASS, SHAPED, HT, SELFCOL, IMIT> sim;
   sim.init(w, k, T, L, env, pool);
   int lane = sim.lane;
   real *qg = gptr(st.qpos) + (size_t)env * h.nq, *vg = gptr(st.qvel) + (size_t)env * h.nv;
