@@ -229,6 +229,19 @@ int ss_set_body_outputs(ss_batch *b, float *xpos, float *xmat);
  * kernel instantiation with the optional outputs. */
 int ss_set_power_output(ss_batch *b, float *power);
 
+/* Optional by-product of ss_step / ss_step_autoreset / ss_imitation_step_fused: per-body contact forces (what users of MuJoCo read
+ * through mjData.efc_force / mj_contactForce, Isaac Gym's net-contact-force tensor): force [N, nbody, 3], float32, caller-owned, world
+ * frame, newtons (NULL = off, the default).  force[n, b] is the net force that all contacts of the LAST mj_step of the control step
+ * exert on body b of env n: the sum over every floor contact of the body and, in self_collision batches, over every body-body
+ * contact — the contact's force with a plus sign on body 2 of the pair and a minus sign on body 1, so these cancel in the sum over
+ * bodies.  A body without an active contact row gets exact zeros.  Row forces are MuJoCo's: f_r = -D * jar_r where jar_r < 0 at the
+ * iterate the solver returned, else 0; a contact's force is sum_r f_r (n + s_r t_r) over its four pyramid rows (r = 0, 1: s = +-mu,
+ * t = t1; r = 2, 3: s = +-mu, t = t2; floor contacts: n = +z).  This is what mjData holds after mj_step: the forces of the forward
+ * pass at the state before the last integration.  Reset launches and the reset forward write nothing; with the in-launch autoreset an
+ * env that was reset keeps the forces of the step that ended its episode (the convention of obs / "final_observation").  Like
+ * ss_set_power_output it selects the kernel instantiation with the optional outputs; the same bits on every run. */
+int ss_set_contact_force_output(ss_batch *b, float *force);
+
 /* Diagnostics for parity triage: one mj_forward at (qpos, qvel) with raw joint torques [N,nu] (NULL = 0);
  * writes the dense joint-space mass matrix [N,nv,nv] (what mj_fullM returns; the stepping path itself never forms
  * it), qfrc_bias [N,nv] and the constrained qacc [N,nv]. */
@@ -278,7 +291,8 @@ enum { SS_FIELD_QPOS = 0,      /* [N,nq] */
        SS_FIELD_BODY_VEL = 4,  /* [N,nbody,6] framelinvel ; frameangvel of the last forward */
        SS_FIELD_TOUCH = 5,     /* [N,2] int32: bit b = body b touches the floor */
        SS_FIELD_QACC_WARM = 6, /* [N,nv] */
-       SS_FIELD_CUR_T = 7 };   /* [N] int32 */
+       SS_FIELD_CUR_T = 7,     /* [N] int32 */
+       SS_FIELD_CONTACT_FORCE = 8 };  /* [N,nbody,3] what the last step wrote (ss_set_contact_force_output; SS_ERR_INVALID while that is off); read-only */
 int ss_get_state(ss_batch *b, int32_t field, void *buf, void *stream);
 int ss_set_state(ss_batch *b, int32_t field, const void *buf, void *stream);
 

@@ -129,6 +129,7 @@ def bind(lib):
     lib.ss_set_order.argtypes = [vp, vp]
     lib.ss_set_body_outputs.argtypes = [vp, vp, vp]
     lib.ss_set_power_output.argtypes = [vp, vp]
+    lib.ss_set_contact_force_output.argtypes = [vp, vp]
     lib.ss_set_launch_geometry.argtypes = [vp, C.c_int32, C.c_int32]
     lib.ss_launch_info.argtypes = [vp] + [C.POINTER(C.c_int32)] * 3
     lib.ss_last_error.argtypes = []; lib.ss_last_error.restype = C.c_char_p
@@ -140,7 +141,7 @@ def bind(lib):
     return lib
 
 
-FIELDS = {"qpos": 0, "qvel": 1, "xpos": 2, "xmat": 3, "body_vel": 4, "touch": 5, "qacc_warm": 6, "cur_t": 7}   # SS_FIELD_*
+FIELDS = {"qpos": 0, "qvel": 1, "xpos": 2, "xmat": 3, "body_vel": 4, "touch": 5, "qacc_warm": 6, "cur_t": 7, "contact_force": 8}   # SS_FIELD_*
 ACTIVATIONS = {"none": 0, "silu": 1, "tanh": 2, "relu": 3}
 MLP_EXPORTS = ["ss_linear_bf16", "ss_linear_bf16_train", "ss_linear_bf16_dx", "ss_wgrad_bf16", "ss_obs_to_bf16", "ss_gaussian_sample",
                "ss_debug_last_gemm", "ss_linear_bf16_dx_det", "ss_linear_bf16_dx_det_workspace", "ss_wgrad_bf16_det", "ss_wgrad_bf16_det_workspace",
@@ -211,7 +212,7 @@ def bind_mlp(lib):
 
 EXPORTS = ["ss_model_create", "ss_model_create_shapes", "ss_model_destroy", "ss_model_dims", "ss_model_elimination_tree", "ss_obs_size", "ss_batch_create",
            "ss_batch_destroy", "ss_reset", "ss_step", "ss_step_autoreset", "ss_substep", "ss_kinematics", "ss_debug_forward", "ss_debug_self_contacts", "ss_debug_self_truncation",
-           "ss_gae", "ss_debug_prof", "ss_set_order", "ss_set_body_outputs", "ss_set_power_output", "ss_set_launch_geometry", "ss_schedule_longest_first", "ss_launch_info", "ss_last_error",
+           "ss_gae", "ss_debug_prof", "ss_set_order", "ss_set_body_outputs", "ss_set_power_output", "ss_set_contact_force_output", "ss_set_launch_geometry", "ss_schedule_longest_first", "ss_launch_info", "ss_last_error",
            "ss_model_create_from_mjcf", "ss_model_last_error", "ss_batch_last_error", "ss_imitation_bind", "ss_imitation_step_fused", "ss_get_state", "ss_set_state", "ss_set_fall_actions",
            "ss_motion_cook", "ss_motion_state_at", "ss_motion_resample", "ss_imitation_step"]
 

@@ -307,6 +307,18 @@ class SMPLSimVecEnv:
             _check(lib().ss_set_power_output(self.handle, _ptr(self.power_usage)))
         return self.power_usage
 
+    def enable_contact_forces(self):
+        """Per-body contact forces (what MuJoCo users read through mjData.efc_force / mj_contactForce, Isaac Gym's net-contact-force
+        tensor): after every following step `self.contact_force` [N, nbody, 3] holds, in the world frame and in newtons, the net force
+        that the contacts of the control step's last mj_step exert on each body — floor contacts and, with self_collision, body-body
+        contacts (equal and opposite on the two bodies); exact zeros for bodies without an active contact.  Resets write nothing:
+        an env that autoreset in the step keeps the forces of the step that ended its episode, like info["final_observation"]
+        (ss_set_contact_force_output; selects the kernel instantiation with this output)."""
+        if getattr(self, "contact_force", None) is None:
+            self.contact_force = torch.zeros(self.num_envs, self.nbody, 3, device=self.device)
+            _check(lib().ss_set_contact_force_output(self.handle, _ptr(self.contact_force)))
+        return self.contact_force
+
     def debug_forward(self, torques=None):
         """(M [N,nv,nv], qfrc_bias, qacc) of one mj_forward at the current state (parity triage)."""
         M = torch.zeros(self.num_envs, self.nv, self.nv, device=self.device)

@@ -77,14 +77,18 @@ kern_t pick_kernel(const ss::KernelKey &key, const ss::Hdr &h, const ss::HdrC &h
 #ifndef SS_NO_FIXED_LAYOUT
   if (key.variant == 0 && !key.bodyout && HdrSmpl::matches(h, hc)) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, false, false, HdrSmpl>;
 #ifndef SS_ONLY_HEADLINE
-  if (key.variant == 0 && plain && key.bodyout && !key.shaped && HdrSmpl::matches(h, hc)) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, false, HdrSmpl>;
-  if (key.variant == 0 && plain && key.shaped && HdrSmpl::matches(h, hc)) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, true, HdrSmpl>;   // per-env body shapes
+  if (key.variant == 0 && plain && key.bodyout && !key.shaped && !key.cforce && HdrSmpl::matches(h, hc)) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, false, HdrSmpl>;
+  if (key.variant == 0 && plain && key.shaped && !key.cforce && HdrSmpl::matches(h, hc)) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, true, HdrSmpl>;   // per-env body shapes
 #endif
 #endif
   if (key.variant == 0 && !key.bodyout) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, false, false>;
 #ifndef SS_ONLY_HEADLINE                                     // (experiment builds, tools/build_variant.sh, keep the headline kernel alone)
   if (key.selfcol) return key.imit ? ss::pick_kernel_imitation_selfcol(key, h, hc) : ss::pick_kernel_selfcol(key, h, hc);
   if (key.imit) return ss::pick_kernel_imitation(key, h, hc);
+  if (key.variant == 0 && key.cforce) {                      // + per-body contact forces
+    if (!key.shaped) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, false, ss::HdrRuntime, false, false, true>;
+    return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, true, ss::HdrRuntime, false, false, true>;
+  }
   if (key.variant == 0) {                                    // SMPL layout (24 bodies)
     if (!key.shaped) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, false>;
     return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, true>;

@@ -7,6 +7,11 @@ namespace ss {
 
 kern_t pick_kernel_imitation(const KernelKey &key, const Hdr &h, const HdrC &hc) {
   const int variant = key.variant;
+  if (key.cforce) {                                              // + per-body contact forces (ss_env_kernel.h)
+    if (variant == 0) return key.shaped ? ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, true, HdrRuntime, false, true, true> : ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, false, HdrRuntime, false, true, true>;
+    if (variant == 1) return key.shaped ? ss_env_kernel<3, 3, 2, 2, SS_MAX_THREADS_X, true, true, HdrRuntime, false, true, true> : ss_env_kernel<3, 3, 2, 2, SS_MAX_THREADS_X, true, false, HdrRuntime, false, true, true>;
+    return nullptr;
+  }
   if (key.shaped) {                                              // per-env body shapes (PHC-style: every env tracks clips with its own body)
     if (variant == 0) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, true, HdrRuntime, false, true>;
     if (variant == 1) return ss_env_kernel<3, 3, 2, 2, SS_MAX_THREADS_X, true, true, HdrRuntime, false, true>;
@@ -26,6 +31,7 @@ kern_t pick_kernel_imitation(const KernelKey &key, const Hdr &h, const HdrC &hc)
 // an all-zero self observation in tests/test_gpu_parity.py::test_fused_imitation_step_with_body_body_contacts_on_gpu); the flags of
 // this unit compile it correctly.
 kern_t pick_kernel_imitation_selfcol(const KernelKey &key, const Hdr &, const HdrC &) {
+  if (key.variant == 0 && !key.shaped && key.cforce) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS_SC, true, false, HdrRuntime, true, true, true>;
   if (key.variant == 0 && !key.shaped) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS_SC, true, false, HdrRuntime, true, true>;
   return nullptr;
 }

@@ -54,6 +54,7 @@ struct ss_batch {
   float *dbg_self = nullptr;              // caller-owned, optional (ss_debug_self_contacts)
   int32_t *self_trunc = nullptr;          // caller-owned, optional [N] (ss_debug_self_truncation)
   float *power = nullptr;                 // caller-owned, optional [N, control_freq_inv, nv - 6] (ss_set_power_output)
+  float *cforce = nullptr;                // caller-owned, optional [N, nbody, 3] (ss_set_contact_force_output)
   int fixed_envs_per_wg = 0, max_wgs = 0; // ss_set_launch_geometry: 0 = automatic (small batches are spread over all CUs)
   mutable std::string err;                // message of the last failed call that took this handle
   mutable int kernel_regs = 0;            // VGPRs of the kernel instantiation this batch launched last (ss_launch_info)
@@ -168,7 +169,7 @@ struct ss_api {
     k.prof = b->d_prof;
     k.order = b->order;
     if (mode == ss::MODE_STEP || mode == ss::MODE_RESET) { k.out0 = ss_batch::R(b->body_xpos); k.out1 = ss_batch::R(b->body_xmat); }
-    if (mode == ss::MODE_STEP) { k.power = ss_batch::R(b->power); k.self_trunc = b->self_trunc; }
+    if (mode == ss::MODE_STEP) { k.power = ss_batch::R(b->power); k.cforce = ss_batch::R(b->cforce); k.self_trunc = b->self_trunc; }
     return k;
   }
   static int run(const ss_batch *b, const ss::KArgs &k, void *stream) {
@@ -272,6 +273,9 @@ struct ss_api {
     switch (field) {
       case SS_FIELD_BODY_VEL: return copy(b->st.body_vel, N * h.nb * 6 * 4);
       case SS_FIELD_TOUCH: return copy(b->st.touch, N * 2 * 4);
+      case SS_FIELD_CONTACT_FORCE:
+        if (!b->cforce) return fail(SS_ERR_INVALID, "SS_FIELD_CONTACT_FORCE: the contact-force output is off (ss_set_contact_force_output)");
+        return copy(b->cforce, N * h.nb * 3 * 4);
       case SS_FIELD_XPOS: case SS_FIELD_XMAT: {
         if (!b->d_kin) b->d_kin = (float *)BE::alloc(N * h.nb * 12 * 4);
         if (!b->d_kin) return fail(SS_ERR_NOMEM, "device allocation failed");
@@ -396,6 +400,7 @@ struct ss_api {
   void ss_batch_destroy(ss_batch *b) { ss_api<BE>::batch_destroy(b); } \
   int ss_set_order(ss_batch *b, const int32_t *order) { ss::HandleScope hs(b); return ss_api<BE>::set(b, &ss_batch::order, order); } \
   int ss_set_power_output(ss_batch *b, float *power) { ss::HandleScope hs(b); return ss_api<BE>::set(b, &ss_batch::power, power); } \
+  int ss_set_contact_force_output(ss_batch *b, float *force) { ss::HandleScope hs(b); return ss_api<BE>::set(b, &ss_batch::cforce, force); } \
   int ss_set_fall_actions(ss_batch *b, const float *fa) { ss::HandleScope hs(b); return ss_api<BE>::set(b, &ss_batch::fall_actions, fa); } \
   int ss_debug_self_truncation(ss_batch *b, int32_t *counts) { ss::HandleScope hs(b); return ss_api<BE>::set(b, &ss_batch::self_trunc, counts); } \
   int ss_debug_self_contacts(ss_batch *b, float *records) { ss::HandleScope hs(b); return ss_api<BE>::set(b, &ss_batch::dbg_self, records); } \

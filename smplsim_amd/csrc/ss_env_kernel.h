@@ -33,9 +33,11 @@ kern_t pick_kernel_x(const KernelKey &key, const Hdr &h, const HdrC &hc);       
 
 namespace {
 
+// CFORCE: the body-output instantiations that also write the per-body contact forces (ss_set_contact_force_output; KernelKey::cforce).
+// They exist with the run-time header only: a batch that asks for the forces runs the generic kernel of its size class.
 // IMIT: the instantiation of ss_imitation_step_fused — after the step pass the wave runs the imitation task of its env and, if the
 // env finished, the reference-state re-initialisation (ss_imfused.h) around the stepper's own reset pass.
-template <int DOFP, int CANDP, int SLOTP, int NPASS, int MAXT, bool BODYOUT, bool SHAPED, class HT = ss::HdrRuntime, bool SELFCOL = false, bool IMIT = false>
+template <int DOFP, int CANDP, int SLOTP, int NPASS, int MAXT, bool BODYOUT, bool SHAPED, class HT = ss::HdrRuntime, bool SELFCOL = false, bool IMIT = false, bool CFORCE = false>
 __global__ void __launch_bounds__(MAXT) ss_env_kernel(const ss::KArgs k) {
   extern __shared__ __align__(16) uint32_t lds[];
   if (blockIdx.x == 0 && threadIdx.x == 0) *k.work_counter_next = 0;   // the next launch's counter (this launch uses the other one)
@@ -71,17 +73,17 @@ __global__ void __launch_bounds__(MAXT) ss_env_kernel(const ss::KArgs k) {
     int mode = k.mode;
     if constexpr (IMIT) {
       const ss::mo::ImFused *f = static_cast<const ss::mo::ImFused *>(k.im);
-      ss::run_env<WaveGpu, DOFP, CANDP, SLOTP, NPASS, BODYOUT, SHAPED, HT, SELFCOL, IMIT>(&w, &k, lds, L, env, mode, pool);
+      ss::run_env<WaveGpu, DOFP, CANDP, SLOTP, NPASS, BODYOUT, SHAPED, HT, SELFCOL, IMIT, CFORCE>(&w, &k, lds, L, env, mode, pool);
       w.sync();
       if (ss::mo::fused_after_step(&w, f, k.im_rand, env)) {
-        ss::run_env<WaveGpu, DOFP, CANDP, SLOTP, NPASS, BODYOUT, SHAPED, HT, SELFCOL, IMIT>(&w, &k, lds, L, env, ss::MODE_RESET, pool);
+        ss::run_env<WaveGpu, DOFP, CANDP, SLOTP, NPASS, BODYOUT, SHAPED, HT, SELFCOL, IMIT, CFORCE>(&w, &k, lds, L, env, ss::MODE_RESET, pool);
         w.sync();
         ss::mo::fused_after_reset(&w, f, env);
       }
       continue;
     }
     for (int rep = 0; rep < 2; rep++) {                       // second trip = fused Default reset of an env whose episode ended
-      const bool again = ss::run_env<WaveGpu, DOFP, CANDP, SLOTP, NPASS, BODYOUT, SHAPED, HT, SELFCOL, IMIT>(&w, &k, lds, L, env, mode, pool);
+      const bool again = ss::run_env<WaveGpu, DOFP, CANDP, SLOTP, NPASS, BODYOUT, SHAPED, HT, SELFCOL, IMIT, CFORCE>(&w, &k, lds, L, env, mode, pool);
       w.sync();
       if (!again) break;
       mode = ss::MODE_RESET;

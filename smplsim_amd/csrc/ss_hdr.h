@@ -343,6 +343,7 @@ struct KArgs {
   real *power;                // optional [N, nsub, nv - 6]: |torque * velocity| per mj_step (ss_set_power_output; body-output instantiations)
   int32_t *self_trunc;        // optional [N]: += 1 per mj_step whose body-body contact list was cut to kMaxSelf (ss_debug_self_truncation)
   HdrC hc;                    // elimination tree of aba_solve / aba_resolve / aba_columns
+  real *cforce;               // optional [N, nb, 3]: net contact force on every body at the control step's last mj_step (ss_set_contact_force_output; body-output instantiations)
 };
 
 // floats of one env's LDS slice for this launch
@@ -354,11 +355,12 @@ inline size_t launch_lds_bytes(const KArgs &k, int e) {
 
 // Which instantiation of the step kernel a launch runs: the size class (kernel_variant) and the template switches.  bodyout is the
 // kernel's BODYOUT, not the caller's wish alone: only the plain kernel exists without the body-frame outputs.
-struct KernelKey { int variant; bool bodyout, shaped, selfcol, imit; };
+struct KernelKey { int variant; bool bodyout, shaped, selfcol, imit, cforce; };   // cforce: the body-output instantiation that also writes the contact forces
 inline KernelKey kernel_key(const KArgs &k) {
-  KernelKey key{kernel_variant(k.h), false, k.st.shape_id != nullptr, k.cfg.self_collision != 0, k.im != nullptr};
-  const bool wanted = (k.out0 || k.power) && (k.mode == MODE_STEP || k.mode == MODE_RESET);
+  KernelKey key{kernel_variant(k.h), false, k.st.shape_id != nullptr, k.cfg.self_collision != 0, k.im != nullptr, false};
+  const bool wanted = (k.out0 || k.power || k.cforce) && (k.mode == MODE_STEP || k.mode == MODE_RESET);
   key.bodyout = wanted || key.shaped || key.selfcol || key.imit;
+  key.cforce = k.cforce && k.mode == MODE_STEP;
   return key;
 }
 

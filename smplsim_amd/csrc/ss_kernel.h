@@ -2394,6 +2394,83 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
   }
 
   // ------------------------------------------------------------------ semi-implicit Euler
+  // ss_set_contact_force_output: the net force (world frame) that the contacts of this mj_step exert on every body, from the constraint
+  // registers (called after the mj_step's last Newton iteration), into Pb[3 body + axis] — Pb is dead between the last newton_finish
+  // and the next newton_prepare; run_env copies it out when the pass sequence has ended (the address arithmetic of the output stays
+  // out of the state machine).  Pb is also V (ss_hdr.h: l_V = l_Pb), the body velocities of forward_kin: the staged forces survive
+  // until the copy-out only because the one pass in between, the K_FINAL forward, runs with with_dyn = false and writes no
+  // velocities — a final forward that does would have to be given another array here.  Row forces are the solver's, f_r = -D jar_r where jar_r < 0 at the iterate newton_finish left.
+  // Floor contacts: the per-lane force and the group sums of newton_prepare; the group's first lane owns the body and writes its
+  // three values — every body has such a lane, so bodies without an active row get zeros and nothing is cleared first.  Body-body
+  // contacts (SELFCOL): the lanes' forces are staged in LDS, the lane of a body adds those on its own body in contact order (+ on
+  // body 2, - on body 1 of the pair) to what its owner lane wrote.  No atomics: the order of every sum is fixed, so the output has
+  // the same bits on every run.
+  SS_DEV void contact_forces() {
+    fresh();
+    typename HT::type h = HT::view(k->h);
+    const real mu = h.mu;
+#pragma unroll
+    for (int p = 0; p < SLOTP; p++) {
+      const Contact &c = con[p];
+      const int sl = p * 64 + lane;
+      const bool boxlane = sl < 4 * h.nbox;
+      real vals[3] = {0.f, 0.f, 0.f};
+      if (c.active) {
+#pragma unroll
+        for (int r_ = 0; r_ < 4; r_++) {
+          const real sgn = (r_ & 1) ? -mu : mu;
+          const real wx = r_ < 2 ? sgn * c.t1x : -sgn * c.t1y;
+          const real wy = r_ < 2 ? sgn * c.t1y : sgn * c.t1x;
+          if (c.jar[r_] < 0.f) {
+            const real f = -c.D * c.jar[r_];
+            vals[0] += f * wx; vals[1] += f * wy; vals[2] += f;
+          }
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < 3; t++) {
+        real v1 = vals[t] + w->quad_xor1(vals[t]);
+        real v2 = w->quad_xor2(v1);
+        vals[t] = boxlane ? v1 + v2 : v1;
+      }
+      const bool leader = (boxlane ? (sl & 3) == 0 : (sl & 1) == 0) && sl < h.nslot;
+      if (leader) { real *o = Pb + 3 * slot_body[p]; o[0] = vals[0]; o[1] = vals[1]; o[2] = vals[2]; }
+    }
+    if constexpr (SELFCOL) {
+      if (this->nself > 0) {
+        const SelfCon &c = this->sc;
+        int act = 0;
+        real fx = 0, fy = 0, fz = 0;
+        if (lane < this->nself) {
+#pragma unroll
+          for (int i = 0; i < 4; i++)
+            if (c.jar[i] < 0) { real d[3]; self_row_dir(i, mu, d); const real f = -c.D * c.jar[i]; fx += f * d[0]; fy += f * d[1]; fz += f * d[2]; act = 1; }
+        }
+        const unsigned long long am = w->ballot(act);
+        if (am) {
+          if (act) {
+            real *o = this->stage + 8 * lane;
+            o[0] = fx; o[1] = fy; o[2] = fz; o[3] = 0.f; o[4] = (real)c.b1; o[5] = (real)c.b2;
+          }
+          w->sync();
+          if (lane < h.nb) {
+            real f0 = 0, f1 = 0, f2 = 0;
+            const real me = (real)lane;
+            for (unsigned long long m_ = am; m_; m_ &= m_ - 1ull) {
+              const real *o = this->stage + 8 * __builtin_ctzll(m_);
+              const float4_t v0 = ld4(o);
+              const real sg = o[5] == me ? real(1) : (o[4] == me ? real(-1) : real(0));
+              f0 += sg * v0.x; f1 += sg * v0.y; f2 += sg * v0.z;
+            }
+            real *pb = Pb + 3 * lane;
+            pb[0] += f0; pb[1] += f1; pb[2] += f2;
+          }
+        }
+      }
+    }
+    w->sync();
+  }
+
   SS_DEV void integrate() {
     fresh();
     typename HT::type h = HT::view(k->h);
@@ -2514,7 +2591,17 @@ enum { SOLVE_NEWTON = 1, SOLVE_SPD = 2 };
 // BODYOUT: the instantiation whose step / reset passes also write the body frames (ss_set_body_outputs).  A separate
 // instantiation because the extra epilogue costs the headline step kernel 3.7% (register allocation of the hot loops
 // shifts) even when the pointer is null — callers that do not ask for it keep the plain one.
-template <class W, int DOFP, int CANDP, int SLOTP, int NPASS, bool BODYOUT = false, bool SHAPED = false, class HT = HdrRuntime, bool SELFCOL = false, bool IMIT = false>
+// CFORCE: the body-output instantiation that also writes the per-body contact forces (ss_set_contact_force_output).  A switch of its
+// own for the reason BODYOUT is one: with the block compiled in and its pointer null, most body-output instantiations (always used by
+// body-body-contact, per-env-shape and imitation batches) needed 8 to 32 more bytes of scratch per lane — callers that do not ask for the
+// forces run the kernels they ran before, instruction for instruction (profiles/contact_force.txt).  Host builds (the wavefront
+// emulator) compile it in and test the pointer at run time, as they do for BODYOUT.
+#if defined(__HIPCC__)
+constexpr bool kContactForceDefault = false;
+#else
+constexpr bool kContactForceDefault = true;
+#endif
+template <class W, int DOFP, int CANDP, int SLOTP, int NPASS, bool BODYOUT = false, bool SHAPED = false, class HT = HdrRuntime, bool SELFCOL = false, bool IMIT = false, bool CFORCE = kContactForceDefault>
 SS_DEV bool run_env(W *w, const KArgs *k, const uint32_t *T, real *L, int env, int mode, real *pool = nullptr) {
   typename HT::type h = HT::view(k->h);
   const ss_env_cfg &cf = k->cfg;
@@ -2680,6 +2767,11 @@ SS_DEV bool run_env(W *w, const KArgs *k, const uint32_t *T, real *L, int env, i
       if constexpr (BODYOUT)                                 // HumanoidEnv.curr_power_usage: |qfrc_actuator * qvel| of this mj_step's torque and the new velocity
         if (k->power && mode == MODE_STEP)
           for (int i = 6 + lane; i < h.nv; i += 64) k->power[((size_t)env * nsub + s) * (h.nv - 6) + i - 6] = SS_M(fabs)(sim.tau[i] * sim.v[i]);
+      // per-body contact forces of the control step's last mj_step (mjData after mj_step: the forces of the forward pass at the state
+      // before this integration), while the constraint registers are live; they wait in LDS for the write-out below.  A redone
+      // mj_step gets here when the redone one completes
+      if constexpr (BODYOUT && CFORCE)
+        if (s == nsub - 1 && mode == MODE_STEP && k->cforce) sim.contact_forces();
       SS_TICK(PF_INTEG);
       if (!next_action) break;
       solve = SOLVE_SPD;
@@ -2702,6 +2794,11 @@ SS_DEV bool run_env(W *w, const KArgs *k, const uint32_t *T, real *L, int env, i
   }
 #endif
 #endif
+  // ss_set_contact_force_output.  `mode` is the parameter: the fused reset pass of an env that just finished writes nothing, so its
+  // row keeps the forces of the step that ended the episode (like obs against obs2)
+  if constexpr (BODYOUT && CFORCE)
+    if (k->cforce && mode == MODE_STEP)
+      for (int i = lane; i < 3 * h.nb; i += 64) k->cforce[(size_t)env * (3 * h.nb) + i] = sim.Pb[i];
   // body frames of the last forward: mj_kinematics readback, and (ss_set_body_outputs) a by-product of every step / reset
   if ((mode == MODE_KINEMATICS || (BODYOUT && k->out0 && !is_debug && mode != MODE_SUBSTEP)) && lane < h.nb) {
     for (int c = 0; c < 3; c++) k->out0[((size_t)env * h.nb + lane) * 3 + c] = sim.r[3 * lane + c] + sim.q[c];

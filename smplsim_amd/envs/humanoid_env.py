@@ -245,6 +245,11 @@ class HumanoidEnv:
     def get_body_xpos(self):
         return self._vec.kinematics()[0][0].cpu().numpy().astype(np.float64)
 
+    def get_body_contact_force(self):
+        """[nbody, 3] net contact force on every body (world frame, N) at the last mj_step of the last control step
+        (SMPLSimVecEnv.enable_contact_forces).  The first call turns the output on: values are valid from the next step on."""
+        return self._vec.enable_contact_forces()[0].cpu().numpy().astype(np.float64)
+
     def get_root_pos(self):
         return self.get_qpos()[:3].copy()
 

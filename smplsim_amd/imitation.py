@@ -165,6 +165,12 @@ class SMPLSimImitationVecEnv:
         info["critic_state"] = self.obs_buf
         return self.obs_buf, self.rew_buf, terminated, truncated, info
 
+    def enable_contact_forces(self):
+        """SMPLSimVecEnv.enable_contact_forces of the stepped batch: `contact_force` [N, nbody, 3], written by every following step,
+        fused or not (a re-initialised env keeps the forces of the step that ended its episode)."""
+        self.contact_force = self.base.enable_contact_forces()
+        return self.contact_force
+
     def reference_actions(self):
         """PD targets that replay the clip: the next frame's joint angles in action units (dof_pos / pi, the reference's own
         replay recipe in examples/motion_lib_test.py:67) — a policy-free tracking baseline."""
