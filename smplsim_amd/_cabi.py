@@ -1,220 +1,108 @@
-"""ctypes declarations of the C ABI in include/smplsim_hip.h and include/smplsim_motion.h (structs + prototypes).
+"""ctypes bindings of the C ABI, derived from include/smplsim_hip.h, smplsim_motion.h and smplsim_mlp.h when this module is imported.
 
-Pure declarations: `bind(cdll)` attaches argtypes/restypes to an already-loaded library.
-The product loads libsmplsim_hip.so through smplsim_amd/_lib.py; tests bind the same
-declarations onto the wavefront-emulator build of the kernel source.
+The headers are the one description of the ABI: _cheader.parse reads their structs, prototypes and integer constants, and `_ctype`
+below is the one mapping from a C type to ctypes.  Nothing here repeats a field list, an argument list, a function name or a
+constant's value; a new entry point is declared in the header and is bound.  tests/test_cabi_cpu.py holds the result against
+clang's reading of the same headers.
+
+`bind(cdll)` attaches the prototypes of smplsim_hip.h and smplsim_motion.h to an already-loaded library, `bind_mlp(cdll)` those of
+smplsim_mlp.h (product library only: the matrix-core kernels).  The product loads libsmplsim_hip.so through smplsim_amd/_lib.py;
+tests bind the same declarations onto the wavefront-emulator build of the kernel source.
 """
 import ctypes as C
+import os
+import re
 
 import numpy as np
 
-TASK_BASE, TASK_SPEED, TASK_GETUP, TASK_REACH = 0, 1, 2, 3
-INIT_DEFAULT, INIT_FALL, INIT_EXTERNAL = 0, 1, 2
-CTRL_UHC_PD, CTRL_PD, CTRL_TORQUE, CTRL_SIMPLE_PID, CTRL_DEFAULT = 0, 1, 2, 3, 4
+from . import _cheader
+
+_INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+HEADERS = {n: _cheader.parse(open(os.path.join(_INCLUDE, n)).read(), n) for n in ("smplsim_hip.h", "smplsim_motion.h", "smplsim_mlp.h")}
+
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
+            "uint8_t": C.c_uint8}
+_PY_NAMES = {"ss_model_desc": "ModelDesc", "ss_env_cfg": "EnvCfg", "ss_state": "State", "ss_mjcf_options": "MjcfOptions", "ss_skeleton": "Skeleton",
+             "ss_motion_data": "MotionData", "ss_motion_state": "MotionState", "ss_imitation_cfg": "ImitationCfg", "ss_imitation_io": "ImitationIO",
+             "ss_adam_tensor": "AdamTensor", "ss_gather_tensor": "GatherTensor"}
+STRUCTS = {}                     # C name -> ctypes.Structure class; the classes are module attributes under their _PY_NAMES
+_OPAQUE = {o for h in HEADERS.values() for o in h.opaque}
+
+
+def _ctype(ctype):
+    """C type (in the spelling of _cheader) -> ctypes, for parameters, results and struct fields alike.  Data pointers and handles are
+    c_void_p (it takes None, an address, byref(...) and an array); only what a caller fills in through ctypes keeps its pointee."""
+    base = " ".join(w for w in re.findall(r"\w+", ctype.split("[")[0]) if w not in ("const", "struct"))
+    stars, bound = ctype.count("*"), re.search(r"\[(\d+)\]$", ctype)
+    if stars == 0:
+        t = None if base == "void" else STRUCTS[base] if base in STRUCTS else _SCALARS[base]
+        return t * int(bound.group(1)) if bound else t
+    if base == "char" and stars <= 2:
+        return C.c_char_p if stars == 1 else C.POINTER(C.c_char_p)
+    if base in STRUCTS and stars == 1:
+        return C.POINTER(STRUCTS[base])
+    if base in _OPAQUE and stars == 2:
+        return C.POINTER(C.c_void_p)
+    return C.c_void_p
+
+
+for _hname, _h in HEADERS.items():
+    for _cname, _fields in _h.structs.items():
+        STRUCTS[_cname] = type(_PY_NAMES[_cname], (C.Structure,), {"_fields_": [(f, _ctype(t)) for f, t in _fields],
+                                                                   "__doc__": f"{_cname} of include/{_hname}"})
+globals().update({c.__name__: c for c in STRUCTS.values()})
+
+# header -> {function: (restype, argtypes)}
+PROTOTYPES = {hname: {f: (_ctype(ret), [_ctype(p) for p in params]) for f, (ret, params) in h.functions.items()} for hname, h in HEADERS.items()}
+EXPORTS = [f for hname in ("smplsim_hip.h", "smplsim_motion.h") for f in PROTOTYPES[hname]]
+MLP_EXPORTS = list(PROTOTYPES["smplsim_mlp.h"])
+
+
+def _bind(lib, *hnames):
+    for hname in hnames:
+        for f, (restype, argtypes) in PROTOTYPES[hname].items():
+            fn = getattr(lib, f)
+            fn.restype, fn.argtypes = restype, argtypes
+    return lib
+
+
+def bind(lib):
+    return _bind(lib, "smplsim_hip.h", "smplsim_motion.h")
+
+
+def bind_mlp(lib):
+    return _bind(lib, "smplsim_mlp.h")
+
+
+CONSTANTS = {k: v for h in HEADERS.values() for k, v in h.constants.items()}      # every enumerator and integer define
+
+
+def _family(prefix, end=None):
+    """{lower-case name: value} of the constants `prefix`*, by value; `end` names the enumerator that closes the family (a count)."""
+    return {k[len(prefix):].lower(): v for k, v in sorted(CONSTANTS.items(), key=lambda kv: kv[1])
+            if k.startswith(prefix) and (end is None or v < CONSTANTS[end])}
+
+
+TASK_BASE, TASK_SPEED, TASK_GETUP, TASK_REACH = (CONSTANTS["SS_TASK_" + n] for n in ("BASE", "SPEED", "GETUP", "REACH"))
+INIT_DEFAULT, INIT_FALL, INIT_EXTERNAL = (CONSTANTS["SS_INIT_" + n] for n in ("DEFAULT", "FALL", "EXTERNAL"))
+CTRL_UHC_PD, CTRL_PD, CTRL_TORQUE, CTRL_SIMPLE_PID, CTRL_DEFAULT = (CONSTANTS["SS_CTRL_" + n] for n in ("UHC_PD", "PD", "TORQUE", "SIMPLE_PID", "DEFAULT"))
+# the names only Python knows: the reference's env classes, control_mode strings and StateInit members
 TASKS = {"HumanoidEnv": TASK_BASE, "HumanoidSpeed": TASK_SPEED, "HumanoidGetup": TASK_GETUP, "HumanoidReach": TASK_REACH}
 CONTROL_MODES = {"uhc_pd": CTRL_UHC_PD, "pd": CTRL_PD, "torque": CTRL_TORQUE, "simple_pid": CTRL_SIMPLE_PID,
                  "default": CTRL_DEFAULT}
 STATE_INITS = {"Default": INIT_DEFAULT, "Fall": INIT_FALL, "External": INIT_EXTERNAL}
-SS_MAX_SELF_CONTACTS = 64        # include/smplsim_hip.h: one body-body contact per lane of the env's wavefront
-
-
-class ModelDesc(C.Structure):
-    _fields_ = [
-        ("nbody", C.c_int32), ("body_parent", C.c_void_p), ("body_pos", C.c_void_p), ("body_mass", C.c_void_p),
-        ("body_ipos", C.c_void_p), ("body_iquat", C.c_void_p), ("body_inertia", C.c_void_p),
-        ("geom_type", C.c_void_p), ("geom_size", C.c_void_p), ("geom_pos", C.c_void_p), ("geom_quat", C.c_void_p),
-        ("dof_armature", C.c_void_p), ("jnt_range", C.c_void_p), ("jnt_limited", C.c_void_p),
-        ("body_invweight0", C.c_void_p), ("dof_invweight0", C.c_void_p), ("qpos0", C.c_void_p),
-        ("nu", C.c_int32), ("actuator_dof", C.c_void_p), ("kp", C.c_void_p), ("kd", C.c_void_p),
-        ("torque_lim", C.c_void_p), ("act_scale", C.c_void_p), ("act_offset", C.c_void_p),
-        ("legal_contact", C.c_void_p),
-        ("timestep", C.c_double), ("gravity", C.c_double), ("solref", C.c_double * 2), ("solimp", C.c_double * 5),
-        ("margin", C.c_double), ("friction", C.c_double), ("impratio", C.c_double),
-        ("geom_contype", C.c_void_p), ("geom_conaffinity", C.c_void_p), ("nexclude", C.c_int32), ("exclude", C.c_void_p),
-        ("meaninertia", C.c_double),
-    ]
-
-
-class EnvCfg(C.Structure):
-    _fields_ = [
-        ("task", C.c_int32), ("state_init", C.c_int32), ("self_obs_v", C.c_int32), ("control_mode", C.c_int32),
-        ("episode_length", C.c_int32), ("control_freq_inv", C.c_int32), ("root_height_obs", C.c_int32),
-        ("power_scale", C.c_float),
-        ("tar_speed_min", C.c_float), ("tar_speed_max", C.c_float), ("speed_change_min", C.c_int32),
-        ("speed_change_max", C.c_int32),
-        ("tar_height_min", C.c_float), ("tar_height_max", C.c_float), ("height_change_min", C.c_int32),
-        ("height_change_max", C.c_int32), ("recovery_steps", C.c_int32), ("newton_iters", C.c_int32),
-        ("tar_dist_max", C.c_float), ("reach_body", C.c_int32), ("self_collision", C.c_int32),
-        ("solver_tolerance", C.c_float),
-    ]
-
-
-class State(C.Structure):
-    _fields_ = [
-        ("num_envs", C.c_int32), ("qpos", C.c_void_p), ("qvel", C.c_void_p), ("qpos_prev", C.c_void_p),
-        ("qvel_prev", C.c_void_p), ("qacc_warm", C.c_void_p), ("body_vel", C.c_void_p), ("touch", C.c_void_p),
-        ("cur_t", C.c_void_p), ("task", C.c_void_p), ("nwarn", C.c_void_p), ("solver_iters", C.c_void_p),
-        ("pid_integral", C.c_void_p), ("pid_last_error", C.c_void_p), ("pid_started", C.c_void_p), ("shape_id", C.c_void_p),
-        ("self_contacts", C.c_void_p),
-    ]
-
-
-class Skeleton(C.Structure):
-    _fields_ = [("nbody", C.c_int32), ("parent", C.c_void_p), ("smpl_2_mujoco", C.c_void_p)]
-
-
-MOTION_DATA_ARRAYS = ("length_starts", "motion_num_frames", "motion_dt", "motion_lengths", "frame_motion", "pose_aa", "trans",
-                      "offsets", "gts", "grs", "lrs", "gvs", "gavs", "dof_pos", "dvs", "qpos", "qvel")
-
-
-class MotionData(C.Structure):
-    _fields_ = [("num_motions", C.c_int32), ("num_frames", C.c_int32), ("nbody", C.c_int32)] + \
-               [(n, C.c_void_p) for n in MOTION_DATA_ARRAYS]
-
-
-MOTION_STATE_FIELDS = ("root_pos", "root_rot", "dof_pos", "root_vel", "root_ang_vel", "dof_vel", "rg_pos", "rb_rot", "body_vel",
-                       "body_ang_vel", "qpos", "qvel")
-
-
-class MotionState(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in MOTION_STATE_FIELDS]
-
-
-class ImitationCfg(C.Structure):
-    _fields_ = [(n, C.c_float) for n in ("k_pos", "k_rot", "k_vel", "k_ang_vel", "w_pos", "w_rot", "w_vel", "w_ang_vel",
-                                         "termination_distance", "obs_dt")]
-
-
-class ImitationIO(C.Structure):
-    _fields_ = [("data", C.POINTER(MotionData)), ("cfg", ImitationCfg), ("motion_ids", C.c_void_p), ("start_times", C.c_void_p),
-                ("offset", C.c_void_p), ("sampling_cdf", C.c_void_p), ("truncate_time", C.c_float), ("random_start", C.c_int32),
-                ("obs_final", C.c_void_p), ("obs_next", C.c_void_p), ("obs_stride", C.c_int32), ("reward", C.c_void_p),
-                ("reward_parts", C.c_void_p), ("terminated", C.c_void_p), ("truncated", C.c_void_p)]
-
-
-class MjcfOptions(C.Structure):
-    _fields_ = [("control_mode", C.c_int32), ("clip_actions", C.c_int32), ("pdp_scale", C.c_double), ("pdd_scale", C.c_double),
-                ("timestep", C.c_double), ("num_contact_bodies", C.c_int32), ("contact_bodies", C.POINTER(C.c_char_p))]
-
-
-def bind(lib):
-    vp = C.c_void_p
-    lib.ss_model_create_from_mjcf.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(MjcfOptions), C.c_int, C.POINTER(vp)]
-    lib.ss_set_fall_actions.argtypes = [vp, vp]
-    lib.ss_get_state.argtypes = [vp, C.c_int32, vp, vp]
-    lib.ss_set_state.argtypes = [vp, C.c_int32, vp, vp]
-    lib.ss_imitation_bind.argtypes = [vp, C.POINTER(ImitationIO)]
-    lib.ss_imitation_step_fused.argtypes = [vp, vp, vp, vp]
-    lib.ss_model_last_error.argtypes = [vp]; lib.ss_model_last_error.restype = C.c_char_p
-    lib.ss_batch_last_error.argtypes = [vp]; lib.ss_batch_last_error.restype = C.c_char_p
-    lib.ss_model_create.argtypes = [C.POINTER(ModelDesc), C.c_int, C.POINTER(vp)]
-    lib.ss_model_create_shapes.argtypes = [C.POINTER(ModelDesc), C.c_int32, C.c_int, C.POINTER(vp)]
-    lib.ss_model_destroy.argtypes = [vp]; lib.ss_model_destroy.restype = None
-    lib.ss_model_dims.argtypes = [vp] + [C.POINTER(C.c_int32)] * 4
-    lib.ss_obs_size.argtypes = [vp, C.POINTER(EnvCfg)]
-    lib.ss_batch_create.argtypes = [vp, C.POINTER(EnvCfg), C.POINTER(State), C.POINTER(vp)]
-    lib.ss_batch_destroy.argtypes = [vp]; lib.ss_batch_destroy.restype = None
-    lib.ss_reset.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.ss_step.argtypes = [vp] * 8
-    lib.ss_substep.argtypes = [vp, vp, C.c_int, vp]
-    lib.ss_kinematics.argtypes = [vp, vp, vp, vp]
-    lib.ss_debug_forward.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.ss_debug_self_contacts.argtypes = [vp, vp]
-    lib.ss_debug_self_truncation.argtypes = [vp, vp]
-    lib.ss_model_elimination_tree.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.ss_step_autoreset.argtypes = [vp] * 10
-    lib.ss_schedule_longest_first.argtypes = [vp, vp]
-    lib.ss_gae.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp, vp]
-    lib.ss_debug_prof.argtypes = [vp, vp, C.c_int]
-    lib.ss_set_order.argtypes = [vp, vp]
-    lib.ss_set_body_outputs.argtypes = [vp, vp, vp]
-    lib.ss_set_power_output.argtypes = [vp, vp]
-    lib.ss_set_contact_force_output.argtypes = [vp, vp]
-    lib.ss_set_launch_geometry.argtypes = [vp, C.c_int32, C.c_int32]
-    lib.ss_launch_info.argtypes = [vp] + [C.POINTER(C.c_int32)] * 3
-    lib.ss_last_error.argtypes = []; lib.ss_last_error.restype = C.c_char_p
-    lib.ss_motion_cook.argtypes = [C.POINTER(Skeleton), C.POINTER(MotionData), C.c_int32, vp]
-    lib.ss_motion_state_at.argtypes = [C.POINTER(MotionData), vp, vp, vp, vp, C.c_int32, C.c_int32, C.POINTER(MotionState), vp]
-    lib.ss_motion_resample.argtypes = [C.POINTER(MotionData), vp, vp, vp, C.c_float, C.c_int32, vp, vp, vp]
-    lib.ss_imitation_step.argtypes = [C.POINTER(MotionData), C.POINTER(ImitationCfg)] + [vp] * 5 + [C.c_int32] + [vp] * 4 + \
-                                     [C.c_int32] + [vp] * 5
-    return lib
-
-
-FIELDS = {"qpos": 0, "qvel": 1, "xpos": 2, "xmat": 3, "body_vel": 4, "touch": 5, "qacc_warm": 6, "cur_t": 7, "contact_force": 8}   # SS_FIELD_*
-ACTIVATIONS = {"none": 0, "silu": 1, "tanh": 2, "relu": 3}
-MLP_EXPORTS = ["ss_linear_bf16", "ss_linear_bf16_train", "ss_linear_bf16_dx", "ss_wgrad_bf16", "ss_obs_to_bf16", "ss_gaussian_sample",
-               "ss_debug_last_gemm", "ss_linear_bf16_dx_det", "ss_linear_bf16_dx_det_workspace", "ss_wgrad_bf16_det", "ss_wgrad_bf16_det_workspace",
-               "ss_ppo_policy_head", "ss_ppo_policy_head_workspace", "ss_value_head", "ss_value_head_workspace", "ss_adam_step", "ss_adam_step_workspace",
-               "ss_running_norm_update", "ss_running_norm_workspace", "ss_gather_rows", "ss_episode_stats", "ss_episode_stats_workspace",
-               "ss_clip_outcomes", "ss_clip_sampling_cdf"]            # include/smplsim_mlp.h (product library only: the matrix-core kernels)
-
-
-class AdamTensor(C.Structure):
-    """ss_adam_tensor of include/smplsim_mlp.h: one tensor of an ss_adam_step call."""
-    _fields_ = [("p", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("g", C.c_void_p), ("w_bf16", C.c_void_p), ("wt_bf16", C.c_void_p),
-                ("rows", C.c_int32), ("cols", C.c_int32), ("ldg", C.c_int32), ("ld_w", C.c_int32), ("ld_wt", C.c_int32)]
-
-
-class GatherTensor(C.Structure):
-    """ss_gather_tensor of include/smplsim_mlp.h: one tensor of an ss_gather_rows call."""
-    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("elem_bytes", C.c_int32), ("cols", C.c_int32), ("ld_src", C.c_int32), ("ld_dst", C.c_int32),
-                ("dst_block_stride", C.c_int32)]
-
-
+SS_MAX_SELF_CONTACTS = CONSTANTS["SS_MAX_SELF_CONTACTS"]           # one body-body contact per lane of the env's wavefront
+FIELDS = _family("SS_FIELD_")                                      # ss_get_state / ss_set_state
+ACTIVATIONS = _family("SS_ACT_")
+NORM_BLOCK_ROWS = CONSTANTS["SS_NORM_BLOCK_ROWS"]                  # rows per (mean, M2) pair in the workspace of ss_running_norm_update
+EPISODE_MAX_PARTS = CONSTANTS["SS_EPISODE_MAX_PARTS"]              # reward terms of one ss_episode_stats call
+EPISODE_STATS = tuple(_family("SS_EP_", "SS_EP_PARTS"))            # the fixed statistics of ss_episode_stats, in the order of `stats`; the P part sums follow
+CLIP_COLUMNS = tuple(_family("SS_CLIP_", "SS_CLIP_COLUMNS"))       # the columns of the [M, 3] int64 counters of ss_clip_outcomes
+MOTION_DATA_ARRAYS = tuple(f for f, t in HEADERS["smplsim_motion.h"].structs["ss_motion_data"] if "*" in t)
+MOTION_STATE_FIELDS = tuple(f for f, _ in HEADERS["smplsim_motion.h"].structs["ss_motion_state"])
+# These two limits have no macro in a public header (smplsim_mlp.h states them in prose, csrc/ holds the numbers): Python constants.
 ADAM_MAX_TENSORS = 32            # tensors of one ss_adam_step call (the table travels in the kernel arguments)
 GATHER_MAX_TENSORS = 8           # tensors of one ss_gather_rows call
-NORM_BLOCK_ROWS = 256            # SS_NORM_BLOCK_ROWS: rows per (mean, M2) pair in the workspace of ss_running_norm_update
-EPISODE_MAX_PARTS = 8            # SS_EPISODE_MAX_PARTS: reward terms of one ss_episode_stats call
-# SS_EP_*: the fixed statistics of ss_episode_stats, in the order of `stats`; the P part sums follow
-EPISODE_STATS = ("num_steps", "num_episodes", "total_episode_reward", "total_episode_len", "min_episode_reward", "max_episode_reward", "total_reward",
-                 "min_reward", "max_reward")
-# SS_CLIP_*: the columns of the [M, 3] int64 counters of ss_clip_outcomes
-CLIP_COLUMNS = ("failed", "completed", "steps")
-
-
-def bind_mlp(lib):
-    vp = C.c_void_p
-    lib.ss_linear_bf16.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
-    lib.ss_linear_bf16_train.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
-    lib.ss_linear_bf16_dx.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
-    lib.ss_wgrad_bf16.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
-    lib.ss_linear_bf16_dx_det.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64, vp]
-    lib.ss_linear_bf16_dx_det_workspace.argtypes = [C.c_int32, C.c_int32, C.c_int32]; lib.ss_linear_bf16_dx_det_workspace.restype = C.c_int64
-    lib.ss_wgrad_bf16_det.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64, vp]
-    lib.ss_wgrad_bf16_det_workspace.argtypes = [C.c_int32, C.c_int32, C.c_int32]; lib.ss_wgrad_bf16_det_workspace.restype = C.c_int64
-    lib.ss_obs_to_bf16.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_float, C.c_float, C.c_float, vp, C.c_int32, vp]
-    lib.ss_gaussian_sample.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_float, C.c_float, vp, vp]
-    lib.ss_debug_last_gemm.argtypes = [C.c_char_p, C.c_int32]
-    # (mean, ldm, actions, lda, log_std, adv, old_logp, M, dim, clip_eps, logp, dmean, ldd, dmean_is_bf16, dlog_std, stats, workspace, bytes, stream)
-    lib.ss_ppo_policy_head.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int64, vp]
-    lib.ss_ppo_policy_head_workspace.argtypes = [C.c_int32, C.c_int32]; lib.ss_ppo_policy_head_workspace.restype = C.c_int64
-    # (pred, target, M, dpred, ldd, dpred_is_bf16, loss, workspace, bytes, stream)
-    lib.ss_value_head.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, C.c_int64, vp]
-    lib.ss_value_head_workspace.argtypes = [C.c_int32]; lib.ss_value_head_workspace.restype = C.c_int64
-    # (tensors, count, step, lr, beta1, beta2, eps, weight_decay, max_grad_norm, grad_norm, workspace, bytes, stream)
-    lib.ss_adam_step.argtypes = [C.POINTER(AdamTensor), C.c_int32, C.c_int32] + [C.c_double] * 6 + [vp, vp, C.c_int64, vp]
-    lib.ss_adam_step_workspace.argtypes = [C.POINTER(AdamTensor), C.c_int32]; lib.ss_adam_step_workspace.restype = C.c_int64
-    # (x, M, dim, ldx, mean, var, std, n, workspace, bytes, stream)
-    lib.ss_running_norm_update.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int64, vp]
-    lib.ss_running_norm_workspace.argtypes = [C.c_int32, C.c_int32]; lib.ss_running_norm_workspace.restype = C.c_int64
-    # (tensors, count, perm, src_rows, rows, block_rows, stream)
-    lib.ss_gather_rows.argtypes = [C.POINTER(GatherTensor), C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp]
-    # (rewards, not_done, parts, T, N, P, ep_return, ep_len, stats, workspace, bytes, stream)
-    lib.ss_episode_stats.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int64, vp]
-    lib.ss_episode_stats_workspace.argtypes = [C.c_int32, C.c_int32, C.c_int32]; lib.ss_episode_stats_workspace.restype = C.c_int64
-    # (clip_ids, dead, done, T, N, M, counts, stream)
-    lib.ss_clip_outcomes.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
-    # (counts, M, uniform_mix, cdf, prob, stream)
-    lib.ss_clip_sampling_cdf.argtypes = [vp, C.c_int32, C.c_double, vp, vp, vp]
-    return lib
-
-
-EXPORTS = ["ss_model_create", "ss_model_create_shapes", "ss_model_destroy", "ss_model_dims", "ss_model_elimination_tree", "ss_obs_size", "ss_batch_create",
-           "ss_batch_destroy", "ss_reset", "ss_step", "ss_step_autoreset", "ss_substep", "ss_kinematics", "ss_debug_forward", "ss_debug_self_contacts", "ss_debug_self_truncation",
-           "ss_gae", "ss_debug_prof", "ss_set_order", "ss_set_body_outputs", "ss_set_power_output", "ss_set_contact_force_output", "ss_set_launch_geometry", "ss_schedule_longest_first", "ss_launch_info", "ss_last_error",
-           "ss_model_create_from_mjcf", "ss_model_last_error", "ss_batch_last_error", "ss_imitation_bind", "ss_imitation_step_fused", "ss_get_state", "ss_set_state", "ss_set_fall_actions",
-           "ss_motion_cook", "ss_motion_state_at", "ss_motion_resample", "ss_imitation_step"]
 
 
 def make_model_desc(mc, kp, kd, torque_lim, act_scale, act_offset, legal_bodies=(), timestep=1.0 / 450):
@@ -257,7 +145,9 @@ def make_env_cfg(task=TASK_BASE, state_init=INIT_DEFAULT, self_obs_v=1, control_
                  tar_speed=(0.0, 5.0), speed_change=(100, 200), tar_height=(0.5, 1.2), height_change=(100, 200),
                  recovery_steps=60, newton_iters=0, tar_dist_max=1.0, reach_body=0, self_collision=False, solver_tolerance=0.0):
     """newton_iters / solver_tolerance: mjOption.iterations / tolerance; 0 = MuJoCo's defaults (100, 1e-8)."""
-    return EnvCfg(task, state_init, self_obs_v, control_mode, episode_length, control_freq_inv, int(root_height_obs),
-                  power_scale, tar_speed[0], tar_speed[1], speed_change[0], speed_change[1], tar_height[0],
-                  tar_height[1], height_change[0], height_change[1], recovery_steps, newton_iters, tar_dist_max, reach_body,
-                  int(bool(self_collision)), solver_tolerance)
+    return EnvCfg(task=task, state_init=state_init, self_obs_v=self_obs_v, control_mode=control_mode, episode_length=episode_length,
+                  control_freq_inv=control_freq_inv, root_height_obs=int(root_height_obs), power_scale=power_scale,
+                  tar_speed_min=tar_speed[0], tar_speed_max=tar_speed[1], speed_change_min=speed_change[0], speed_change_max=speed_change[1],
+                  tar_height_min=tar_height[0], tar_height_max=tar_height[1], height_change_min=height_change[0],
+                  height_change_max=height_change[1], recovery_steps=recovery_steps, newton_iters=newton_iters, tar_dist_max=tar_dist_max,
+                  reach_body=reach_body, self_collision=int(bool(self_collision)), solver_tolerance=solver_tolerance)

@@ -105,3 +105,18 @@ def lib():
         import torch  # noqa: F401
         _LIB = _cabi.bind_mlp(_cabi.bind(ctypes.CDLL(LIB_PATH)))
     return _LIB
+
+
+# The three helpers of every call into the library (also importable from smplsim_amd.batch, where they used to live).
+def _check(rc):
+    if rc != 0:
+        raise RuntimeError(f"libsmplsim_hip error {rc}: {lib().ss_last_error().decode()}")
+
+
+def _ptr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _launch_stream(device):
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)

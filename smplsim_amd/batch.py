@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _cabi
-from ._lib import lib
+from ._lib import _check, _launch_stream, _ptr, lib  # noqa: F401  (the three helpers stay importable from here)
 from .gains import build_pd_tables
 from .mjcf import compile_mjcf
 from .mjcf_writer import default_xml_str
@@ -22,24 +22,11 @@ from .mjcf_writer import default_xml_str
 DEFAULT_CONTACT_BODIES = ("R_Ankle", "L_Ankle", "R_Toe", "L_Toe")
 
 
-def _check(rc):
-    if rc != 0:
-        raise RuntimeError(f"libsmplsim_hip error {rc}: {lib().ss_last_error().decode()}")
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def _shard_device(index):
     """The device the shard's tensors live on: always a ROCm GPU (there is no CPU path in this package)."""
     if not torch.cuda.is_available():
         raise RuntimeError("SMPLSimVecEnv needs a ROCm GPU (MI355X); there is no CPU fallback")
     return torch.device("cuda", int(index))
-
-
-def _launch_stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 _WARNED = False
@@ -102,8 +89,9 @@ class ShardModel:
             h = C.c_void_p()
             if a["compiler"] == "native":
                 names = (C.c_char_p * len(a["contact_bodies"]))(*[n.encode() for n in a["contact_bodies"]])
-                opt = _cabi.MjcfOptions(_cabi.CONTROL_MODES[a["control_mode"]], int(bool(a["clip_actions"])), a["pdp_scale"], a["pdd_scale"],
-                                        1.0 / a["sim_timestep_inv"], len(a["contact_bodies"]), names)
+                opt = _cabi.MjcfOptions(control_mode=_cabi.CONTROL_MODES[a["control_mode"]], clip_actions=int(bool(a["clip_actions"])),
+                                        pdp_scale=a["pdp_scale"], pdd_scale=a["pdd_scale"], timestep=1.0 / a["sim_timestep_inv"],
+                                        num_contact_bodies=len(a["contact_bodies"]), contact_bodies=names)
                 txt = self.xml.encode()
                 _check(lib().ss_model_create_from_mjcf(txt, len(txt), C.byref(opt), self.device, C.byref(h)))
             else:
@@ -178,10 +166,10 @@ class SMPLSimVecEnv:
             self.shape_id = sid.to(torch.int32).contiguous()
         elif shape_id is not None:
             raise ValueError("shape_id given but the model has a single shape (build it with ShardModel(xmls=[...]))")
-        st = _cabi.State(N, *[_ptr(t) for t in (self.qpos, self.qvel, self.qpos_prev, self.qvel_prev, self.qacc_warm,
-                                               self.body_vel, self.touch, self.cur_t, self.task_state, self.nwarn,
-                                               self.solver_iters, self.pid_integral, self.pid_last_error,
-                                               self.pid_started, self.shape_id, self.self_contacts)])
+        st = _cabi.State(num_envs=N, task=_ptr(self.task_state),
+                         **{f: _ptr(getattr(self, f)) for f in ("qpos", "qvel", "qpos_prev", "qvel_prev", "qacc_warm", "body_vel", "touch", "cur_t",
+                                                                "nwarn", "solver_iters", "pid_integral", "pid_last_error", "pid_started",
+                                                                "shape_id", "self_contacts")})
         self.handle = C.c_void_p()
         _check(lib().ss_batch_create(self.model.handle, C.byref(self.cfg), C.byref(st), C.byref(self.handle)))
         self.obs_size = lib().ss_obs_size(self.model.handle, C.byref(self.cfg))

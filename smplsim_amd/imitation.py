@@ -20,8 +20,8 @@ import ctypes as C
 import torch
 
 from . import _cabi
-from .batch import SMPLSimVecEnv, _check, _ptr
-from ._lib import lib
+from .batch import SMPLSimVecEnv
+from ._lib import _check, _ptr, lib
 
 
 class SMPLSimImitationVecEnv:
@@ -41,7 +41,9 @@ class SMPLSimImitationVecEnv:
             raise ValueError("motion library and env must live on the same device")
         self.num_envs, self.device, self.nbody = b.num_envs, b.device, b.nbody
         self.dt = control_freq_inv / float(sim_timestep_inv)
-        self.cfg = _cabi.ImitationCfg(*reward_k, *reward_w, termination_distance, self.dt)
+        terms = self.reward_part_names
+        self.cfg = _cabi.ImitationCfg(**{"k_" + t: k for t, k in zip(terms, reward_k)}, **{"w_" + t: w for t, w in zip(terms, reward_w)},
+                                      termination_distance=termination_distance, obs_dt=self.dt)
         self.random_start, self.autoreset = random_start, autoreset
         N, J, dev = self.num_envs, self.nbody, self.device
         f32 = dict(dtype=torch.float32, device=dev)
@@ -76,9 +78,11 @@ class SMPLSimImitationVecEnv:
         ml = self.motion_lib
         if not self.fused or self._bound == ml.load_count:
             return
-        io = _cabi.ImitationIO(C.pointer(ml.data), self.cfg, *[_ptr(t) for t in (self.motion_ids, self.start_times, self.offset,
-                               ml.sampling_cdf)], self.dt, int(bool(self.random_start)), _ptr(self.obs_final), _ptr(self.obs_buf),
-                               self.obs_size, _ptr(self.rew_buf), _ptr(self.reward_parts), _ptr(self.terminated), _ptr(self.truncated))
+        io = _cabi.ImitationIO(data=C.pointer(ml.data), cfg=self.cfg, motion_ids=_ptr(self.motion_ids), start_times=_ptr(self.start_times),
+                               offset=_ptr(self.offset), sampling_cdf=_ptr(ml.sampling_cdf), truncate_time=self.dt,
+                               random_start=int(bool(self.random_start)), obs_final=_ptr(self.obs_final), obs_next=_ptr(self.obs_buf),
+                               obs_stride=self.obs_size, reward=_ptr(self.rew_buf), reward_parts=_ptr(self.reward_parts),
+                               terminated=_ptr(self.terminated), truncated=_ptr(self.truncated))
         _check(lib().ss_imitation_bind(self.base.handle, C.byref(io)))
         self._bound = ml.load_count
 

@@ -109,8 +109,7 @@ class ClipOutcomes:
         if self.device.type != "cuda":
             clip_outcomes_host(clip_ids.numpy(), dead.numpy(), done.numpy(), self.counts.numpy())
         else:
-            from .._lib import lib
-            from ..batch import _check, _launch_stream, _ptr
+            from .._lib import _check, _launch_stream, _ptr, lib
             T, N = clip_ids.shape
             _check(lib().ss_clip_outcomes(_ptr(clip_ids), _ptr(dead), _ptr(done), T, N, self.num_clips, _ptr(self.counts), _launch_stream(self.device)))
         self.last = self.counts[:, :STEPS].sum(0) - before
@@ -128,8 +127,7 @@ class ClipOutcomes:
             cdf.copy_(torch.from_numpy(c))
             self.prob.copy_(torch.from_numpy(p))
         else:
-            from .._lib import lib
-            from ..batch import _check, _launch_stream, _ptr
+            from .._lib import _check, _launch_stream, _ptr, lib
             _check(lib().ss_clip_sampling_cdf(_ptr(self.counts), self.num_clips, self.uniform_mix, _ptr(cdf), _ptr(self.prob), _launch_stream(self.device)))
         return self.prob
 

@@ -105,8 +105,7 @@ class EpisodeStats:
         if self.device.type != "cuda":
             out = episode_stats_host(rewards.numpy(), not_done.numpy(), None if parts is None else parts.numpy(), self.ep_return.numpy(), self.ep_len.numpy())
             return torch.from_numpy(out)
-        from .._lib import lib
-        from ..batch import _check, _launch_stream, _ptr
+        from .._lib import _check, _launch_stream, _ptr, lib
         L = lib()
         stats = torch.empty(NFIXED + P, dtype=torch.float64, device=self.device)
         ws = self._ws.get(self.device, L.ss_episode_stats_workspace(T, N, P))

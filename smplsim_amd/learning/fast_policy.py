@@ -14,8 +14,7 @@ import math
 import torch
 
 from .. import _cabi
-from .._lib import lib
-from ..batch import _check, _launch_stream, _ptr
+from .._lib import _check, _launch_stream, _ptr, lib
 from .fused_train import _pad
 
 

@@ -14,8 +14,7 @@ keeps one workspace (learning/_scratch.py), so two calls of one object must not 
 """
 import torch
 
-from .._lib import lib
-from ..batch import _check, _launch_stream, _ptr
+from .._lib import _check, _launch_stream, _ptr, lib
 from ._scratch import Scratch
 
 

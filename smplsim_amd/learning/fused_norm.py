@@ -13,8 +13,7 @@ One stream per object (its workspace and its operand are shared between its call
 """
 import torch
 
-from .._lib import lib
-from ..batch import _check, _launch_stream, _ptr
+from .._lib import _check, _launch_stream, _ptr, lib
 from ._scratch import Scratch
 from .fused_train import Bf16Operand, _pad
 

@@ -17,8 +17,7 @@ import ctypes
 import torch
 
 from .. import _cabi
-from .._lib import lib
-from ..batch import _check, _launch_stream
+from .._lib import _check, _launch_stream, lib
 from ._scratch import Scratch
 
 _REFUSED = ("amsgrad", "maximize", "capturable", "differentiable", "decoupled_weight_decay")
@@ -108,8 +107,9 @@ class LibAdam(torch.optim.Adam):
                 g = g.contiguous()
                 rows, cols, ldg = 1, n, n
         w, wt = images.get(id(p), (None, None))
-        d = _cabi.AdamTensor(p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), g.data_ptr(), None if w is None else w.data_ptr(),
-                             None if wt is None else wt.data_ptr(), rows, cols, ldg, 0 if w is None else w.stride(0), 0 if wt is None else wt.stride(0))
+        d = _cabi.AdamTensor(p=p.data_ptr(), m=st["exp_avg"].data_ptr(), v=st["exp_avg_sq"].data_ptr(), g=g.data_ptr(),
+                             w_bf16=None if w is None else w.data_ptr(), wt_bf16=None if wt is None else wt.data_ptr(), rows=rows, cols=cols, ldg=ldg,
+                             ld_w=0 if w is None else w.stride(0), ld_wt=0 if wt is None else wt.stride(0))
         return d, g
 
     @torch.no_grad()

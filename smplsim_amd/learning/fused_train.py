@@ -32,8 +32,7 @@ import weakref
 import torch
 
 from .. import _cabi
-from .._lib import lib
-from ..batch import _check, _launch_stream, _ptr
+from .._lib import _check, _launch_stream, _ptr, lib
 from ._scratch import Scratch
 
 

@@ -6,8 +6,7 @@ never leaves the GPU.
 """
 import torch
 
-from .._lib import lib
-from ..batch import _check, _ptr
+from .._lib import _check, _ptr, lib
 
 
 def estimate_advantages_columns(rewards, not_done, not_dead, values, gamma, tau, bootstrap=None):

@@ -109,12 +109,12 @@ class ShuffledBatch:
                 s.dst.view(self.num_blocks, s.stride, s.cols)[:, :self.B, :s.gcols] = rows.view(self.num_blocks, self.B, s.cols)[:, :, :s.gcols]
             return
         from .. import _cabi
-        from .._lib import lib
-        from ..batch import _check, _launch_stream, _ptr
+        from .._lib import _check, _launch_stream, _ptr, lib
         perm = perm if perm.is_contiguous() else perm.contiguous()
         table = (_cabi.GatherTensor * len(self.items))()
         for j, s in enumerate(self.items):
-            table[j] = _cabi.GatherTensor(s.src.data_ptr(), s.dst.data_ptr(), s.src.element_size(), s.gcols, s.src.stride(0), s.dst.stride(0), s.stride)
+            table[j] = _cabi.GatherTensor(src=s.src.data_ptr(), dst=s.dst.data_ptr(), elem_bytes=s.src.element_size(), cols=s.gcols, ld_src=s.src.stride(0),
+                                          ld_dst=s.dst.stride(0), dst_block_stride=s.stride)
         _check(lib().ss_gather_rows(table, len(self.items), _ptr(perm), self.M, n, self.B, _launch_stream(self.device)))
         for s in self.items:
             torch.autograd.graph.increment_version(s.dst)          # written in place behind torch's back: say so

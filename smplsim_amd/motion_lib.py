@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _cabi
+from ._lib import _ptr
 
 SMPL_BONE_ORDER_NAMES = ["Pelvis", "L_Hip", "R_Hip", "Torso", "L_Knee", "R_Knee", "Spine", "L_Ankle", "R_Ankle", "Chest", "L_Toe",
                          "R_Toe", "Neck", "L_Thorax", "R_Thorax", "Head", "L_Shoulder", "R_Shoulder", "L_Elbow", "R_Elbow",
@@ -59,10 +60,6 @@ class Skeleton:
         return cls(mc.body_names, mc.body_parent, mc.body_pos, smpl_order_names,
                    geoms=(np.asarray(mc.geom_type), np.asarray(mc.geom_size, np.float32), np.asarray(mc.geom_pos, np.float32),
                           np.asarray(mc.geom_quat, np.float32)))
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def qpos_to_pose_aa(qpos, skeleton):
@@ -228,10 +225,10 @@ class MotionLibSMPL:
         self.grvs, self.gravs = self.gvs[:, 0], self.gavs[:, 0]
         self._d.update(gts=self.gts, grs=self.grs, lrs=self.lrs, gvs=self.gvs, gavs=self.gavs, dof_pos=self.dof_pos, dvs=self.dvs,
                        qpos=self.qpos, qvel=self.qvel)
-        self.data = _cabi.MotionData(M, F, J, *[_ptr(self._d[n]) for n in _cabi.MOTION_DATA_ARRAYS])
+        self.data = _cabi.MotionData(num_motions=M, num_frames=F, nbody=J, **{n: _ptr(self._d[n]) for n in _cabi.MOTION_DATA_ARRAYS})
         sk = self.skeleton
         self._sk_keep = (np.ascontiguousarray(sk.parents, np.int32), np.ascontiguousarray(sk.smpl_2_mujoco, np.int32))
-        skel = _cabi.Skeleton(J, self._sk_keep[0].ctypes.data_as(C.c_void_p), self._sk_keep[1].ctypes.data_as(C.c_void_p))
+        skel = _cabi.Skeleton(nbody=J, parent=self._sk_keep[0].ctypes.data_as(C.c_void_p), smpl_2_mujoco=self._sk_keep[1].ctypes.data_as(C.c_void_p))
         self._check(self._lib.ss_motion_cook(C.byref(skel), C.byref(self.data), int(self.filter_vel), self._stream()))
         if self.fix_height == FixHeightMode.geom_fix:
             self._geom_height_fix()
@@ -403,7 +400,7 @@ class MotionLibSMPL:
                       dof_vel=(N, 3 * (J - 1)), rg_pos=(N, J, 3), rb_rot=(N, J, 4), body_vel=(N, J, 3), body_ang_vel=(N, J, 3),
                       qpos=(N, 7 + 3 * (J - 1)), qvel=(N, 6 + 3 * (J - 1)))
         out = {k: torch.empty(shapes[k], dtype=torch.float32, device=self.device) for k in fields}
-        st = _cabi.MotionState(*[_ptr(out.get(k)) for k in _cabi.MOTION_STATE_FIELDS])
+        st = _cabi.MotionState(**{k: _ptr(t) for k, t in out.items()})
         self._keep = (ids, times, off, out)
         self._check(self._lib.ss_motion_state_at(C.byref(self.data), _ptr(ids), _ptr(times), _ptr(off), None, N, int(intervaled),
                                                  C.byref(st), self._stream()))

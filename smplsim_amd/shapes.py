@@ -74,7 +74,7 @@ class ShapeVariedVecEnv:
             # concurrent launches share the GPU as full workgroups on 1/K of the CUs each (a spread small batch would claim
             # every CU's LDS and the launches would run one after the other)
             import ctypes as C
-            from .batch import _check, lib
+            from ._lib import _check, lib
             cus = torch.cuda.get_device_properties(self.device).multi_processor_count
             for e in self.envs:
                 _check(lib().ss_set_launch_geometry(e.handle, C.c_int32(e.launch_info()["envs_per_workgroup"]), C.c_int32(max(1, cus // K))))
