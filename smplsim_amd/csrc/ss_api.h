@@ -95,7 +95,11 @@ struct ss_api {
     if (num_shapes > 1 && 12 * hm.h_sc.nb > hm.h_sc.l_Wst - hm.h_sc.l_IA) { delete m; return fail(SS_ERR_LDS, "no room for the per-env body offsets"); }   // (the aliased layout has the 12 nb by construction)
     m->num_shapes = num_shapes; m->device = device;
     if (!BE::set_device(device)) { delete m; return fail(SS_ERR_HIP, "cannot select device"); }
-    if (!(up(m->d_shared, hm.shared) && up(m->d_bodyc, hm.bodyc) && up(m->d_candc, hm.candc) && up(m->d_candb, hm.candb) && up(m->d_pairs, hm.pairs) && up(m->d_geomc, hm.geomc))) {
+    // (the shared table: the blob, and behind it the chain records, ss_hdr.h chain_rec_goffset)
+    std::vector<uint32_t> tables = hm.shared;
+    tables.resize((size_t)ss::chain_rec_goffset(hm.h), 0u);
+    tables.insert(tables.end(), hm.chainrec.begin(), hm.chainrec.end());
+    if (!(up(m->d_shared, tables) && up(m->d_bodyc, hm.bodyc) && up(m->d_candc, hm.candc) && up(m->d_candb, hm.candb) && up(m->d_pairs, hm.pairs) && up(m->d_geomc, hm.geomc))) {
       model_destroy(m);                                      // (a table that failed is null: everything allocated so far is freed once)
       return fail(SS_ERR_HIP, "device table upload failed");
     }
@@ -134,7 +138,7 @@ struct ss_api {
     if (b->cfg.newton_iters <= 0) b->cfg.newton_iters = 100;
     b->cfg.solver_tolerance = (float)((cfg->solver_tolerance > 0.f ? (double)cfg->solver_tolerance : 1e-8) * m->hm.meaninertia * (h.nv > 1 ? h.nv : 1));
     b->obs_size = ss::obs_size(h, *cfg);
-    size_t shared_b = (size_t)((h.shared_words + 3) & ~3) * 4;
+    size_t shared_b = (size_t)ss::lds_table_words(h) * 4;   // the blob's LDS copy and the chain records
     const size_t env_b = (size_t)(cfg->self_collision ? m->hm.sc.env_floats : h.env_floats) * sizeof(ss::real);
     int cap = BE::lds_capacity();
     const size_t pool_b = cfg->self_collision ? (size_t)ss::ss_pool_floats(m->hm.sc) * sizeof(ss::real) : 0;   // the workgroup's shared dense block

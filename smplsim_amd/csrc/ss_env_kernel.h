@@ -41,18 +41,20 @@ template <int DOFP, int CANDP, int SLOTP, int NPASS, int MAXT, bool BODYOUT, boo
 __global__ void __launch_bounds__(MAXT) ss_env_kernel(const ss::KArgs k) {
   extern __shared__ __align__(16) uint32_t lds[];
   if (blockIdx.x == 0 && threadIdx.x == 0) *k.work_counter_next = 0;   // the next launch's counter (this launch uses the other one)
-  for (int i = threadIdx.x; i < k.h.shared_words; i += blockDim.x) lds[i] = k.shared_g[i];
+  // the workgroup's tables: the blob's prefix, then the chain records, which lie behind the whole blob in the global copy (ss_hdr.h)
+  const int tables = ss::lds_table_words(k.h), rec_shift = ss::chain_rec_goffset(k.h) - ss::chain_rec_offset(k.h);
+  for (int i = threadIdx.x; i < tables; i += blockDim.x) lds[i] = k.shared_g[i < k.h.shared_words ? i : i + rec_shift];
   if constexpr (SELFCOL)                                     // lock word of the shared dense block (ss_hdr.h), free
     if (threadIdx.x == 0 && ss::ss_pool_floats(k.sc) > 0)
-      *reinterpret_cast<int *>(reinterpret_cast<float *>(lds + ((k.h.shared_words + 3) & ~3)) + (size_t)(blockDim.x >> 6) * k.sc.env_floats) = 0;
+      *reinterpret_cast<int *>(reinterpret_cast<float *>(lds + tables) + (size_t)(blockDim.x >> 6) * k.sc.env_floats) = 0;
   __syncthreads();
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform -> LDS bases stay in SGPRs
   const int slice = SELFCOL ? k.sc.env_floats : HT::view(k.h).env_floats;
-  float *L = reinterpret_cast<float *>(lds + ((k.h.shared_words + 3) & ~3)) + (size_t)wave * slice;
+  float *L = reinterpret_cast<float *>(lds + tables) + (size_t)wave * slice;
   float *pool = nullptr;                                     // SELFCOL: the workgroup's shared dense block behind the env slices (ss_hdr.h)
   if constexpr (SELFCOL) {
     if (ss::ss_pool_floats(k.sc) > 0) {
-      pool = reinterpret_cast<float *>(lds + ((k.h.shared_words + 3) & ~3)) + (size_t)(blockDim.x >> 6) * slice;
+      pool = reinterpret_cast<float *>(lds + tables) + (size_t)(blockDim.x >> 6) * slice;
     }
   }
   WaveGpu w{(int)(threadIdx.x & 63)};

@@ -23,6 +23,12 @@ namespace ss { typedef float real; }
 #define SS_LS_MAXIT 16
 #endif
 
+#if defined(__HIPCC__)
+#define SS_HD __host__ __device__ inline __attribute__((always_inline))
+#else
+#define SS_HD inline __attribute__((always_inline))
+#endif
+
 namespace ss {
 
 constexpr int kWave = 64;
@@ -136,6 +142,17 @@ constexpr bool alias_layout_fits(int nb, int maxlev, int nslot) {
   return ((6 * nb + 3) & ~3) <= 48 * maxlev && y.l_w2 + ((6 * nn + 3) & ~3) <= y.l_R && 13 * nslot <= y.l_R - y.l_An;
 }
 
+// Chain records (built by ss_tables.h chain_records; read by forward_kin's chain sums, ss_kernel.h chain_sum_rec): per node one record of
+// bytes — its depth, then for every level of the node tree the node on its chain from the root at that level, the node itself from
+// its own depth on — padded to whole 16-byte units, so that a lane has everything about its chain after one wide LDS read instead
+// of a table read per chain entry.  Bytes, not premultiplied 16-bit offsets: SMPL-X has 1040 bytes of LDS to spare at its 7 envs
+// per CU, which 53 records of 16 bytes fit and 53 of 32 do not.  The records are a table of their own behind the LDS copy of the
+// shared blob (the blob and the fields of Hdr are what they were; chain_rec_offset below).
+constexpr int chain_rec_bytes(int nlev) { return (1 + nlev + 15) & ~15; }
+constexpr int chain_rec_words(int nn, int nlev) { return nn * (chain_rec_bytes(nlev) / 4); }
+// levels of the node tree (Hdr::nlev) of the two packaged humanoids: the record length of the fixed-layout instantiations
+constexpr int fixed_chain_levels(int nb) { return nb == 24 ? 10 : nb == 52 ? 12 : 0; }
+
 // Body-body contacts (SELFCOL instantiations, ss_env_cfg.self_collision): extra per-env LDS arrays behind the base layout and the
 // static pair table.  Kept out of Hdr: Hdr's layout is part of the plain kernels' register allocation.
 //
@@ -217,13 +234,15 @@ struct HdrC {
 // count, dof counts and the whole LDS layout are compile-time constants — LDS addresses become one base register plus an
 // instruction immediate and ~30 wave-uniform values leave the SGPR file (the generic kernel reloads spilled SGPRs with
 // ~1300 v_readlane per instantiation) — everything else is still read from the runtime header.
-#if defined(__HIPCC__)
-#define SS_HD __host__ __device__ inline __attribute__((always_inline))
-#else
-#define SS_HD inline __attribute__((always_inline))
-#endif
 SS_HD int hdr_o_arm(const Hdr &h) { return (int)(h.arm_lean & 0xffffffffull); }
 SS_HD bool hdr_lean(const Hdr &h) { return (h.arm_lean >> 32) != 0ull; }
+// Where the chain records lie, in 32-bit words: in LDS behind the copy of the blob's prefix, in the global copy of the tables behind the
+// whole blob (lean tables: the dof constants, the blob's last table, lie behind the prefix).  One device buffer, one copy loop.
+SS_HD int chain_rec_offset(const Hdr &h) { return (h.shared_words + 3) & ~3; }
+SS_HD int chain_rec_goffset(const Hdr &h) { return hdr_lean(h) ? ((h.o_dofc + h.nv * kDofC) * (int)(sizeof(real) / 4) + 3) & ~3 : chain_rec_offset(h); }
+// the workgroup's tables: blob, records.  (A multiple of 4 by construction; the mask says so to the compiler, which otherwise loses the
+// 16-byte alignment of the env slices behind the tables and with it every 8- and 16-byte LDS access of the kernel.)
+SS_HD int lds_table_words(const Hdr &h) { return (chain_rec_offset(h) + chain_rec_words(h.nn, h.nlev)) & ~3; }
 struct HdrRuntime {
   typedef const Hdr &type;
   static constexpr bool fixed = false;
@@ -247,6 +266,7 @@ template <int NB, int MAXLEV, bool ALIAS = false>
 struct HdrFixed {
   static constexpr Layout LY = make_layout(NB, MAXLEV, ALIAS);
   static constexpr int nb = NB, nn = NB + 1, nv = 6 + 3 * (NB - 1), nq = 7 + 3 * (NB - 1), maxlev = MAXLEV;
+  static constexpr int chain_levels = fixed_chain_levels(NB);   // = nlev (matches): the chain records' length as a constant
   static constexpr int l_q = LY.l_q, l_v = LY.l_v, l_a = LY.l_a, l_tau = LY.l_tau, l_Fb = LY.l_Fb, l_Pb = LY.l_Pb, l_delta = LY.l_delta,
                        l_diag = LY.l_diag, l_S = LY.l_S, l_Ab = LY.l_Ab, l_An = LY.l_An, l_Aown = LY.l_Aown, l_IA = LY.l_IA,
                        l_Ubuf = LY.l_Ubuf, l_Wst = LY.l_Wst, l_R = LY.l_R, l_r = LY.l_r, l_Gb = LY.l_Gb, l_tmp = LY.l_tmp, l_V = LY.l_V,
@@ -276,7 +296,7 @@ struct HdrFixedT {
   typedef const TreeFixed<NLEV, ROOT, PEL, NK0, CP, CH, NG> tree_type;
   static SS_HD TreeFixed<NLEV, ROOT, PEL, NK0, CP, CH, NG> tree(const HdrC &c) { TreeFixed<NLEV, ROOT, PEL, NK0, CP, CH, NG> t; t.o_lev = c.o_lev; return t; }
   static bool matches(const Hdr &h, const HdrC &c) {
-    return h.nb == NB && h.maxlev == MAXLEV && h.a_stride == (ALIAS ? 24 : 21) && hdr_lean(h) == LEAN && h.env_floats == HdrFixed<NB, MAXLEV, ALIAS>::env_floats && c.nlev == NLEV && c.root == ROOT && c.pel_level == PEL && c.nkpack[0] == NK0 && c.nkpack[1] == 0ull && c.cpack == CP && c.chain == CH && c.neg == NG;
+    return h.nb == NB && h.nlev == fixed_chain_levels(NB) && h.maxlev == MAXLEV && h.a_stride == (ALIAS ? 24 : 21) && hdr_lean(h) == LEAN && h.env_floats == HdrFixed<NB, MAXLEV, ALIAS>::env_floats && c.nlev == NLEV && c.root == ROOT && c.pel_level == PEL && c.nkpack[0] == NK0 && c.nkpack[1] == 0ull && c.cpack == CP && c.chain == CH && c.neg == NG;
   }
 };
 
@@ -350,7 +370,7 @@ struct KArgs {
 inline int env_slice_floats(const KArgs &k) { return k.cfg.self_collision ? k.sc.env_floats : k.h.env_floats; }
 // bytes of dynamic LDS of a launch with e envs per workgroup
 inline size_t launch_lds_bytes(const KArgs &k, int e) {
-  return (size_t)((k.h.shared_words + 3) & ~3) * 4 + ((size_t)e * env_slice_floats(k) + (k.cfg.self_collision ? ss_pool_floats(k.sc) : 0)) * sizeof(real);
+  return (size_t)lds_table_words(k.h) * 4 + ((size_t)e * env_slice_floats(k) + (k.cfg.self_collision ? ss_pool_floats(k.sc) : 0)) * sizeof(real);
 }
 
 // Which instantiation of the step kernel a launch runs: the size class (kernel_variant) and the template switches.  bodyout is the

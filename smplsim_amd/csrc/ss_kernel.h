@@ -322,10 +322,72 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
     w->sync();
     chain_sum(tmp, A);
   }
+  // The chain records of ss_hdr.h in chain_sum, in the fixed-layout instantiations: a lane's depth and the nodes of its whole chain
+  // arrive with one 16-byte read per kRecUnits (one for both humanoids), where the loop below reads the depth, then per group of
+  // four chain entries four table words, then the data: 1 + 2 * groups dependent LDS round trips per trip, all but the last for
+  // constants of the model.  With a runtime tree the record length is no constant and the loop stays (same values either way).
+  static constexpr bool kChainRec = HT::fixed;
+  static constexpr int chain_levels_c() { if constexpr (HT::fixed) return HT::type::chain_levels; else return 1; }
+  static constexpr int kRecUnits = chain_rec_bytes(chain_levels_c()) / 16;
+  struct alignas(16) rec4_t { uint32_t x, y, z, w; };
+  // the records: behind the LDS copy of the blob's prefix; the emulator runs on the global tables (T), where they lie behind the blob
+  SS_DEV const uint32_t *chain_recs() const {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return T + chain_rec_offset(k->h);
+#else
+    return T + chain_rec_goffset(k->h);
+#endif
+  }
+  SS_DEV void rec_read(int n, uint32_t *rw) const {
+    const rec4_t *p = reinterpret_cast<const rec4_t *>(chain_recs()) + n * kRecUnits;
+#pragma unroll
+    for (int u = 0; u < kRecUnits; u++) { const rec4_t v = p[u]; rw[4 * u] = v.x; rw[4 * u + 1] = v.y; rw[4 * u + 2] = v.z; rw[4 * u + 3] = v.w; }
+  }
+  SS_DEV static int rec_depth(const uint32_t *rw) { return (int)(rw[0] & 0xffu); }
+  // the node at level lev of the chain (lev: a constant after unrolling)
+  SS_DEV static int rec_node(const uint32_t *rw, int lev) { return (int)((rw[(1 + lev) >> 2] >> (8 * ((1 + lev) & 3))) & 0xffu); }
+  // chain_sum on the records: per trip of 64 values the record, then all data reads at once (an entry past the depth reads the
+  // node's own row and is selected to zero): two round trips.  The sums keep the loop's association: groups of four in order, and
+  // a group past the depth leaves the sum alone by a select, never by an added zero group (the loop does not execute it).  The
+  // trips stay a loop: unrolled, the reads of all trips are in flight at once and the registers they need are not there.
+  template <bool TWO>
+  SS_DEV void chain_sum_rec(const real *tmp, real *A, const real *tmp2, real *A2) {
+    typename HT::type h = HT::view(k->h);
+    constexpr int NL = chain_levels_c(), NG = (NL + 3) / 4;
+#pragma unroll 1
+    for (int idx = lane; idx < 6 * h.nb; idx += 64) {
+      const int b = idx / 6, c = idx - 6 * b;
+      uint32_t rw[4 * kRecUnits];
+      rec_read(b + 1, rw);
+      const int dn = rec_depth(rw);
+      const real *p = tmp + c, *p2 = tmp2 + c;
+      real a[4 * NG], e[4 * NG];
+#pragma unroll
+      for (int u = 0; u < 4 * NG; u++) {
+        const int nu = 6 * rec_node(rw, u < NL ? u : NL - 1);
+        a[u] = p[nu];
+        if constexpr (TWO) e[u] = p2[nu];
+      }
+      real s = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int g = 0; g < NG; g++) {
+        const int kk = 4 * g;
+        const real ga = (a[kk] + (kk + 1 <= dn ? a[kk + 1] : 0.f)) + ((kk + 2 <= dn ? a[kk + 2] : 0.f) + (kk + 3 <= dn ? a[kk + 3] : 0.f));
+        s = kk <= dn ? s + ga : s;
+        if constexpr (TWO) {
+          const real ge = (e[kk] + (kk + 1 <= dn ? e[kk + 1] : 0.f)) + ((kk + 2 <= dn ? e[kk + 2] : 0.f) + (kk + 3 <= dn ? e[kk + 3] : 0.f));
+          s2 = kk <= dn ? s2 + ge : s2;
+        }
+      }
+      A[idx] = s;
+      if constexpr (TWO) A2[idx] = s2;
+    }
+  }
   // A[b] = sum of the node contributions tmp[n] (6 floats each) over the chain root .. node(b); optionally a second
   // (tmp2 -> A2) pair in the same pass over the chain table
   SS_DEV void chain_sum(const real *tmp, real *A, const real *tmp2 = nullptr, real *A2 = nullptr) {
     typename HT::type h = HT::view(k->h);
+    if constexpr (kChainRec) { if (tmp2) chain_sum_rec<true>(tmp, A, tmp2, A2); else chain_sum_rec<false>(tmp, A, tmp, A); return; }
     for (int idx = lane; idx < 6 * h.nb; idx += 64) {
       int b = idx / 6, c = idx - 6 * b, n = b + 1;
       const int dn = ti(h.o_ndepth, n), row = h.o_chainnode + n * h.nlev;

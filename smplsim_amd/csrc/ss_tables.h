@@ -28,6 +28,7 @@ struct HostModel {
   double meaninertia = 0;         // mjModel.stat.meaninertia (scale of the solver's termination test); shape 0's
   std::string self_collision_unavailable;   // non-empty: the model cannot run with ss_env_cfg.self_collision (reason)
   std::vector<uint32_t> shared;   // tables copied into LDS once per workgroup: integer tables, then the real-valued ones
+  std::vector<uint32_t> chainrec; // chain records (ss_hdr.h): uploaded behind the blob, copied into LDS behind its prefix
   std::vector<int32_t> candb;     // [ncand] body of each candidate, bit 8: capsule
   // one block per body shape: [nb][kBodyC] off3 ipos3 mass Ibody6 invw_tr (loaded into registers; several shapes: + the dof inverse weights,
   // shape_stride), [ncand][kCandC], [nb][kGeomC] geoms in their body frames (pair functions of the SELFCOL kernels)
@@ -37,6 +38,7 @@ struct HostModel {
 };
 struct Tree {   // everything that follows from body_parent alone
   std::vector<int> parent, chainnode, ndepth; int nlev = 0;    // node_tree
+  std::vector<uint32_t> chainrec;                              // chain_records
   std::vector<int> sum_small, sum_big, sum_cover;              // subtree_sum_tables
   HdrC hc{}; int maxlev = 1;                                   // elimination_tree (hc.o_lev: assemble_blob); maxlev = its widest level
   std::vector<int> levrec, towards, joint, negated;            //   the level records of HdrC::o_lev; per body: neighbour towards the root (255: it is the root), joint node, S negated
@@ -144,6 +146,19 @@ inline const char *node_tree(Tree &t) {
   for (int n = 0; n < nn; n++)
     for (int a = n; a >= 0; a = nparent[a]) t.chainnode[n * t.nlev + t.ndepth[a]] = a;
   return nullptr;
+}
+
+// The chain records of ss_hdr.h from the node tree: per node chain_rec_bytes(nlev) bytes, four to a 32-bit word, lowest first — the node's
+// depth, then per level k the node chainnode[n][k] for k <= depth and the node itself behind it (a reader that clamps nothing reads
+// a valid row there and selects it away).
+inline void chain_records(Tree &t) {
+  const int nn = (int)t.ndepth.size(), nby = chain_rec_bytes(t.nlev);
+  t.chainrec.assign((size_t)chain_rec_words(nn, t.nlev), 0u);
+  auto put = [&](int n, int i, uint32_t v) { t.chainrec[(size_t)n * (nby / 4) + i / 4] |= v << (8 * (i & 3)); };
+  for (int n = 0; n < nn; n++) {
+    put(n, 0, (uint32_t)t.ndepth[n]);
+    for (int k = 0; k + 1 < nby; k++) put(n, 1 + k, (uint32_t)(k <= t.ndepth[n] ? t.chainnode[n * t.nlev + k] : n));
+  }
 }
 
 // Subtree sums in two phases (ss_kernel.h subtree_sum).  Bodies are in depth-first order, so the subtree of b is the index range
@@ -397,6 +412,7 @@ inline const char *describe(const ss_model_desc &d, const Topology *like, Topolo
   t.tree.parent.assign(d.body_parent, d.body_parent + nb);
   if (!like || like->tree.parent != t.tree.parent) {
     if (const char *e = node_tree(t.tree)) return e;
+    chain_records(t.tree);
     subtree_sum_tables(t.tree);
     if (const char *e = elimination_tree(t.tree)) return e;
   }
@@ -504,7 +520,7 @@ inline std::string build_host_model(const ss_model_desc *d, int num_shapes, bool
   const Tree &tree = top.tree;
   Hdr &h = out.h = top.h;
   h.nlev = tree.nlev; h.maxlev = tree.maxlev; h.n_sumsmall = (int)tree.sum_small.size(); h.n_sumbig = (int)tree.sum_big.size();
-  out.hc = tree.hc; out.candb = top.candb; out.illegal_mask = top.illegal_mask; out.meaninertia = first.meaninertia;
+  out.hc = tree.hc; out.chainrec = tree.chainrec; out.candb = top.candb; out.illegal_mask = top.illegal_mask; out.meaninertia = first.meaninertia;
   const bool alias = h.nb > 32 && alias_layout_fits(h.nb, h.maxlev, h.nslot) && !plain_layout;
   out.shared = assemble_blob(top, num_shapes == 1 ? &first : nullptr, alias, h, out.hc);
   if (const char *e = lds_layouts(alias, out)) return e;
