@@ -1,4 +1,4 @@
-"""ctypes bindings of the C ABI, derived from include/smplsim_hip.h, smplsim_motion.h and smplsim_mlp.h when this module is imported.
+"""ctypes bindings of the C ABI, derived from include/smplsim_hip.h, smplsim_motion.h, smplsim_mlp.h and smplsim_wrench.h when this module is imported.
 
 The headers are the one description of the ABI: _cheader.parse reads their structs, prototypes and integer constants, and `_ctype`
 below is the one mapping from a C type to ctypes.  Nothing here repeats a field list, an argument list, a function name or a
@@ -6,7 +6,7 @@ constant's value; a new entry point is declared in the header and is bound.  tes
 clang's reading of the same headers.
 
 `bind(cdll)` attaches the prototypes of smplsim_hip.h and smplsim_motion.h to an already-loaded library, `bind_mlp(cdll)` those of
-smplsim_mlp.h (product library only: the matrix-core kernels).  The product loads libsmplsim_hip.so through smplsim_amd/_lib.py;
+smplsim_mlp.h (product library only: the matrix-core kernels), `bind_wrench(cdll)` that of smplsim_wrench.h (the body-wrench input).  The product loads libsmplsim_hip.so through smplsim_amd/_lib.py;
 tests bind the same declarations onto the wavefront-emulator build of the kernel source.
 """
 import ctypes as C
@@ -18,7 +18,7 @@ import numpy as np
 from . import _cheader
 
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
-HEADERS = {n: _cheader.parse(open(os.path.join(_INCLUDE, n)).read(), n) for n in ("smplsim_hip.h", "smplsim_motion.h", "smplsim_mlp.h")}
+HEADERS = {n: _cheader.parse(open(os.path.join(_INCLUDE, n)).read(), n) for n in ("smplsim_hip.h", "smplsim_motion.h", "smplsim_mlp.h", "smplsim_wrench.h")}
 
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
             "uint8_t": C.c_uint8}
@@ -56,6 +56,7 @@ globals().update({c.__name__: c for c in STRUCTS.values()})
 PROTOTYPES = {hname: {f: (_ctype(ret), [_ctype(p) for p in params]) for f, (ret, params) in h.functions.items()} for hname, h in HEADERS.items()}
 EXPORTS = [f for hname in ("smplsim_hip.h", "smplsim_motion.h") for f in PROTOTYPES[hname]]
 MLP_EXPORTS = list(PROTOTYPES["smplsim_mlp.h"])
+WRENCH_EXPORTS = list(PROTOTYPES["smplsim_wrench.h"])
 
 
 def _bind(lib, *hnames):
@@ -72,6 +73,10 @@ def bind(lib):
 
 def bind_mlp(lib):
     return _bind(lib, "smplsim_mlp.h")
+
+
+def bind_wrench(lib):
+    return _bind(lib, "smplsim_wrench.h")
 
 
 CONSTANTS = {k: v for h in HEADERS.values() for k, v in h.constants.items()}      # every enumerator and integer define

@@ -103,7 +103,7 @@ def lib():
         # torch first: it brings its own libamdhip64; loaded after ours (which links /opt/rocm's) the process would hold two HIP
         # runtimes and the first hipSetDevice fails ("cannot select device")
         import torch  # noqa: F401
-        _LIB = _cabi.bind_mlp(_cabi.bind(ctypes.CDLL(LIB_PATH)))
+        _LIB = _cabi.bind_wrench(_cabi.bind_mlp(_cabi.bind(ctypes.CDLL(LIB_PATH))))
     return _LIB
 
 

@@ -307,6 +307,23 @@ class SMPLSimVecEnv:
             _check(lib().ss_set_contact_force_output(self.handle, _ptr(self.contact_force)))
         return self.contact_force
 
+    def enable_body_wrenches(self):
+        """External body wrenches, MuJoCo's mjData.xfrc_applied for the batch: returns `self.xfrc_applied`, a zero tensor
+        [N, nbody, 6] that the caller edits in place — columns 0-2 a force in newtons at the body's centre of mass, columns 3-5 a
+        torque in N m, world frame, indexed by env id.  Every following step / substep / debug_forward applies it, constant over
+        the control step's mj_steps, as part of the smooth force only: qfrc_bias and so the Stable-PD controller do not see it.
+        Resets never apply it (neither reset() nor the in-launch reset of a finished env); an env that a bad state resets inside a
+        launch ignores it for the rest of that launch (mj_resetData zeroes xfrc_applied; the tensor itself is never written by a
+        launch).  ss_set_body_wrench_input; selects the kernel instantiation with the optional inputs and outputs."""
+        if getattr(self, "xfrc_applied", None) is None:
+            self.xfrc_applied = torch.zeros(self.num_envs, self.nbody, 6, device=self.device)
+        _check(lib().ss_set_body_wrench_input(self.handle, _ptr(self.xfrc_applied)))
+        return self.xfrc_applied
+
+    def disable_body_wrenches(self):
+        """Steps stop reading `self.xfrc_applied` (the tensor keeps its contents; enable_body_wrenches attaches it again)."""
+        _check(lib().ss_set_body_wrench_input(self.handle, None))
+
     def debug_forward(self, torques=None):
         """(M [N,nv,nv], qfrc_bias, qacc) of one mj_forward at the current state (parity triage)."""
         M = torch.zeros(self.num_envs, self.nv, self.nv, device=self.device)

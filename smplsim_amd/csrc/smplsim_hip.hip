@@ -85,7 +85,7 @@ kern_t pick_kernel(const ss::KernelKey &key, const ss::Hdr &h, const ss::HdrC &h
 #ifndef SS_ONLY_HEADLINE                                     // (experiment builds, tools/build_variant.sh, keep the headline kernel alone)
   if (key.selfcol) return key.imit ? ss::pick_kernel_imitation_selfcol(key, h, hc) : ss::pick_kernel_selfcol(key, h, hc);
   if (key.imit) return ss::pick_kernel_imitation(key, h, hc);
-  if (key.variant == 0 && key.cforce) {                      // + per-body contact forces
+  if (key.variant == 0 && key.cforce) {                      // optional I/O: contact-force output, body-wrench input
     if (!key.shaped) return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, false, ss::HdrRuntime, false, false, true>;
     return ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, true, ss::HdrRuntime, false, false, true>;
   }

@@ -7,7 +7,7 @@ namespace ss {
 
 kern_t pick_kernel_imitation(const KernelKey &key, const Hdr &h, const HdrC &hc) {
   const int variant = key.variant;
-  if (key.cforce) {                                              // + per-body contact forces (ss_env_kernel.h)
+  if (key.cforce) {                                              // optional I/O: contact-force output, body-wrench input (ss_env_kernel.h)
     if (variant == 0) return key.shaped ? ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, true, HdrRuntime, false, true, true> : ss_env_kernel<2, 2, 1, 1, SS_MAX_THREADS, true, false, HdrRuntime, false, true, true>;
     if (variant == 1) return key.shaped ? ss_env_kernel<3, 3, 2, 2, SS_MAX_THREADS_X, true, true, HdrRuntime, false, true, true> : ss_env_kernel<3, 3, 2, 2, SS_MAX_THREADS_X, true, false, HdrRuntime, false, true, true>;
     return nullptr;

@@ -12,7 +12,7 @@ kern_t pick_kernel_x(const KernelKey &key, const Hdr &h, const HdrC &hc) {
   if (!key.bodyout && HdrSmplx::matches(h, hc)) return ss_env_kernel<3, 3, 2, 2, SS_MAX_THREADS_X, false, false, HdrSmplx>;
 #endif
   if (!key.bodyout) return ss_env_kernel<3, 3, 2, 2, SS_MAX_THREADS_X, false, false>;
-  if (key.cforce) {                                          // + per-body contact forces
+  if (key.cforce) {                                          // optional I/O: contact-force output, body-wrench input
     if (!key.shaped) return ss_env_kernel<3, 3, 2, 2, SS_MAX_THREADS_X, true, false, HdrRuntime, false, false, true>;
     return ss_env_kernel<3, 3, 2, 2, SS_MAX_THREADS_X, true, true, HdrRuntime, false, false, true>;
   }

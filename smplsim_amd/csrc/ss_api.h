@@ -13,6 +13,7 @@
 #include <new>
 #include <string>
 
+#include "../../include/smplsim_wrench.h"
 #include "ss_imfused.h"
 #include "ss_mjcf.h"
 #include "ss_tables.h"
@@ -55,6 +56,7 @@ struct ss_batch {
   int32_t *self_trunc = nullptr;          // caller-owned, optional [N] (ss_debug_self_truncation)
   float *power = nullptr;                 // caller-owned, optional [N, control_freq_inv, nv - 6] (ss_set_power_output)
   float *cforce = nullptr;                // caller-owned, optional [N, nbody, 3] (ss_set_contact_force_output)
+  const float *xfrc = nullptr;            // caller-owned, optional [N, nbody, 6] (ss_set_body_wrench_input)
   int fixed_envs_per_wg = 0, max_wgs = 0; // ss_set_launch_geometry: 0 = automatic (small batches are spread over all CUs)
   mutable std::string err;                // message of the last failed call that took this handle
   mutable int kernel_regs = 0;            // VGPRs of the kernel instantiation this batch launched last (ss_launch_info)
@@ -174,6 +176,8 @@ struct ss_api {
     k.order = b->order;
     if (mode == ss::MODE_STEP || mode == ss::MODE_RESET) { k.out0 = ss_batch::R(b->body_xpos); k.out1 = ss_batch::R(b->body_xmat); }
     if (mode == ss::MODE_STEP) { k.power = ss_batch::R(b->power); k.cforce = ss_batch::R(b->cforce); k.self_trunc = b->self_trunc; }
+    // the body wrenches act wherever mj_steps of the caller's own run (the fused reset pass of a step launch skips them in the kernel), never in a reset launch
+    if (mode == ss::MODE_STEP || mode == ss::MODE_SUBSTEP || mode == ss::MODE_DEBUG_FORWARD) k.xfrc = ss_batch::R(b->xfrc);
     return k;
   }
   static int run(const ss_batch *b, const ss::KArgs &k, void *stream) {
@@ -388,7 +392,7 @@ struct ss_api {
   }
 };
 
-// The extern "C" surface of include/smplsim_hip.h for a backend.  Used once per library, by the translation unit that owns the backend
+// The extern "C" surface of include/smplsim_hip.h (and smplsim_wrench.h) for a backend.  Used once per library, by the translation unit that owns the backend
 // (smplsim_hip.hip; tests/wave_emu/emu.cpp; tests/host_paths_check.cpp).  Every entry is one line: it opens the handle's error scope
 // (ss::HandleScope) and delegates to ss_api<BE>, which checks the handle and everything else.
 #define SS_DEFINE_C_API(BE) \
@@ -405,6 +409,7 @@ struct ss_api {
   int ss_set_order(ss_batch *b, const int32_t *order) { ss::HandleScope hs(b); return ss_api<BE>::set(b, &ss_batch::order, order); } \
   int ss_set_power_output(ss_batch *b, float *power) { ss::HandleScope hs(b); return ss_api<BE>::set(b, &ss_batch::power, power); } \
   int ss_set_contact_force_output(ss_batch *b, float *force) { ss::HandleScope hs(b); return ss_api<BE>::set(b, &ss_batch::cforce, force); } \
+  int ss_set_body_wrench_input(ss_batch *b, const float *wrench) { ss::HandleScope hs(b); return ss_api<BE>::set(b, &ss_batch::xfrc, wrench); } \
   int ss_set_fall_actions(ss_batch *b, const float *fa) { ss::HandleScope hs(b); return ss_api<BE>::set(b, &ss_batch::fall_actions, fa); } \
   int ss_debug_self_truncation(ss_batch *b, int32_t *counts) { ss::HandleScope hs(b); return ss_api<BE>::set(b, &ss_batch::self_trunc, counts); } \
   int ss_debug_self_contacts(ss_batch *b, float *records) { ss::HandleScope hs(b); return ss_api<BE>::set(b, &ss_batch::dbg_self, records); } \

@@ -34,7 +34,8 @@ kern_t pick_kernel_x(const KernelKey &key, const Hdr &h, const HdrC &hc);       
 namespace {
 
 // CFORCE: the body-output instantiations that also write the per-body contact forces (ss_set_contact_force_output; KernelKey::cforce).
-// They exist with the run-time header only: a batch that asks for the forces runs the generic kernel of its size class.
+// They exist with the run-time header only: a batch that asks for the forces runs the generic kernel of its size class.  They are
+// also the instantiations that apply the body wrenches (ss_set_body_wrench_input): either of the two selects them.
 // IMIT: the instantiation of ss_imitation_step_fused — after the step pass the wave runs the imitation task of its env and, if the
 // env finished, the reference-state re-initialisation (ss_imfused.h) around the stepper's own reset pass.
 template <int DOFP, int CANDP, int SLOTP, int NPASS, int MAXT, bool BODYOUT, bool SHAPED, class HT = ss::HdrRuntime, bool SELFCOL = false, bool IMIT = false, bool CFORCE = false>

@@ -364,6 +364,7 @@ struct KArgs {
   int32_t *self_trunc;        // optional [N]: += 1 per mj_step whose body-body contact list was cut to kMaxSelf (ss_debug_self_truncation)
   HdrC hc;                    // elimination tree of aba_solve / aba_resolve / aba_columns
   real *cforce;               // optional [N, nb, 3]: net contact force on every body at the control step's last mj_step (ss_set_contact_force_output; body-output instantiations)
+  const real *xfrc;           // optional [N, nb, 6]: external wrench on every body, world frame, force at the centre of mass ; torque — MuJoCo's xfrc_applied (ss_set_body_wrench_input; the same instantiations)
 };
 
 // floats of one env's LDS slice for this launch
@@ -375,12 +376,14 @@ inline size_t launch_lds_bytes(const KArgs &k, int e) {
 
 // Which instantiation of the step kernel a launch runs: the size class (kernel_variant) and the template switches.  bodyout is the
 // kernel's BODYOUT, not the caller's wish alone: only the plain kernel exists without the body-frame outputs.
-struct KernelKey { int variant; bool bodyout, shaped, selfcol, imit, cforce; };   // cforce: the body-output instantiation that also writes the contact forces
+// cforce: the body-output instantiation with the optional I/O — it writes the contact forces (k.cforce) and applies the body wrenches
+// (k.xfrc), each tested at run time; chosen when either is attached.  The wrench also acts in ss_substep and ss_debug_forward.
+struct KernelKey { int variant; bool bodyout, shaped, selfcol, imit, cforce; };
 inline KernelKey kernel_key(const KArgs &k) {
   KernelKey key{kernel_variant(k.h), false, k.st.shape_id != nullptr, k.cfg.self_collision != 0, k.im != nullptr, false};
   const bool wanted = (k.out0 || k.power || k.cforce) && (k.mode == MODE_STEP || k.mode == MODE_RESET);
-  key.bodyout = wanted || key.shaped || key.selfcol || key.imit;
-  key.cforce = k.cforce && k.mode == MODE_STEP;
+  key.cforce = (k.cforce && k.mode == MODE_STEP) || k.xfrc;   // (ss_api.h hands xfrc over in the modes that apply it only)
+  key.bodyout = wanted || key.shaped || key.selfcol || key.imit || key.cforce;
   return key;
 }
 

@@ -142,8 +142,13 @@ template <> struct SelfColState<true> {
 template <bool MAYBE_LEAN> struct LeanState { const real *act_g = nullptr; SS_DEV const real *action_ptr() const { return act_g; } SS_DEV void set_action_ptr(const real *p) { act_g = p; } };
 template <> struct LeanState<false> { SS_DEV const real *action_ptr() const { return nullptr; } SS_DEV void set_action_ptr(const real *) {} };
 
-template <class W, int DOFP, int CANDP, int SLOTP, int NPASS, bool SHAPED = false, class HT = HdrRuntime, bool SELFCOL = false, bool IMIT = false>
-struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lean> {
+// the body-wrench input (ss_set_body_wrench_input): this env's rows of it while they act, else null.  Like the lean pointer a member of the
+// optional-I/O instantiations only (run_env sets it, reset_data drops it, newton_prepare reads it): the other kernels stay as they were
+template <bool XFRC> struct WrenchState { const real *xfrc = nullptr; SS_DEV const real *wrench_ptr() const { return xfrc; } SS_DEV void set_wrench_ptr(const real *p) { xfrc = p; } };
+template <> struct WrenchState<false> { SS_DEV const real *wrench_ptr() const { return nullptr; } SS_DEV void set_wrench_ptr(const real *) {} };
+
+template <class W, int DOFP, int CANDP, int SLOTP, int NPASS, bool SHAPED = false, class HT = HdrRuntime, bool SELFCOL = false, bool IMIT = false, bool XFRC = false>
+struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lean>, WrenchState<XFRC> {
   W *w;
   const KArgs *k;
   const uint32_t *T;      // shared tables in LDS (integer tables, then the real-valued ones)
@@ -2037,12 +2042,31 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
 
   // right-hand side of the Newton system in two parts — joint space (-> delta) and per-body forces Pb —, diagonal terms
   // and the per-body generalized inertias Aown = I_b + K_b
+  // XFRC (the optional-I/O instantiations): the external wrench of ss_set_body_wrench_input, MuJoCo's xfrc_applied — a force f at the
+  // body's centre of mass c and a torque t, world frame — is one more per-body force next to the contacts': Pb_b -= (c x f + t ; f),
+  // the contact term's reference point (the root origin: forward_kin builds Iown and Fb about it, so c = Iown[1..3] / Iown[0]), axes,
+  // order and sign.  It is part of Pb only, never of Fb: Fb is qfrc_bias, the stale bias of the next Stable-PD solve, which must not
+  // see it.  newton_finish takes its gradient from the same Pb, so no other stage knows of the wrench.  The six values are read
+  // from HBM here, per Newton iteration, by the lane that owns the body: nothing is staged in LDS or kept across the solve.
   SS_DEV void newton_prepare() {
     fresh();
     typename HT::type h = HT::view(k->h);
     const real mu = h.mu;
     iters++;
     SS_FT0();
+    real xw[XFRC ? SLOTP : 1][6];
+    if constexpr (XFRC) {
+      const real *xfrc = this->wrench_ptr();
+#pragma unroll
+      for (int p = 0; p < SLOTP; p++) {
+#pragma unroll
+        for (int t = 0; t < 6; t++) xw[p][t] = 0.f;
+        if (xfrc) {                                            // (wave-uniform; slot_body is a body of the model in every lane)
+#pragma unroll
+          for (int t = 0; t < 6; t++) xw[p][t] = xfrc[6 * slot_body[p] + t];
+        }
+      }
+    }
     // ---- contact forces and K_b = sum_rows D u u^T, u = (rho x w ; w).  The (<= 4) contacts of a box sit in
     // 4 adjacent lanes and the 2 ends of a capsule in 2 adjacent lanes (slot layout of make_constraints), so the
     // per-body sums are quad shuffles; the group's first lane owns the body: it writes the body's inertial force
@@ -2103,6 +2127,13 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
 #pragma unroll
         for (int t = 0; t < 6; t++) g[t] = Ia[t] + vals[t] + Fb[6 * b + t];
         const real m = I[0], cx = I[1], cy = I[2], cz = I[3];
+        if constexpr (XFRC) {                                  // -(c x f + t ; f); zeros while the input is off (x - 0 = x: the same bits)
+          const real im = m > 0.f ? 1.f / m : 0.f;
+          const real px = cx * im, py = cy * im, pz = cz * im;
+          const real *x = xw[p];
+          g[0] -= (py * x[2] - pz * x[1]) + x[3]; g[1] -= (pz * x[0] - px * x[2]) + x[4]; g[2] -= (px * x[1] - py * x[0]) + x[5];
+          g[3] -= x[0]; g[4] -= x[1]; g[5] -= x[2];
+        }
         o[0] = I[4] + vals[6]; o[1] = I[5] + vals[7]; o[2] = I[6] + vals[8]; o[3] = vals[9]; o[4] = vals[10] - cz; o[5] = vals[11] + cy;
         o[6] = I[7] + vals[12]; o[7] = I[8] + vals[13]; o[8] = vals[14] + cz; o[9] = vals[15]; o[10] = vals[16] - cx;
         o[11] = I[9] + vals[17]; o[12] = vals[18] - cy; o[13] = vals[19] + cx; o[14] = vals[20];
@@ -2580,6 +2611,7 @@ struct Sim : ShapeTables<SHAPED>, SelfColState<SELFCOL>, LeanState<HT::maybe_lea
     w->sync();
     if (lane == 0) { q[0] = h.qpos0_root[0]; q[1] = h.qpos0_root[1]; q[2] = h.qpos0_root[2]; q[3] = 1.f; }
     nwarn_add++;
+    this->set_wrench_ptr(nullptr);                            // mj_resetData zeroes xfrc_applied: no wrench for the rest of this launch (the caller's buffer stays)
     w->sync();
   }
 
@@ -2658,6 +2690,9 @@ enum { SOLVE_NEWTON = 1, SOLVE_SPD = 2 };
 // body-body-contact, per-env-shape and imitation batches) needed 8 to 32 more bytes of scratch per lane — callers that do not ask for the
 // forces run the kernels they ran before, instruction for instruction (profiles/contact_force.txt).  Host builds (the wavefront
 // emulator) compile it in and test the pointer at run time, as they do for BODYOUT.
+// The same instantiations hold the body-wrench input (ss_set_body_wrench_input; Sim's XFRC, k->xfrc tested at run time):
+// they are the optional-I/O instantiations, selected when either is attached (KernelKey::cforce) — for the wrench also in ss_substep and
+// ss_debug_forward.  Nothing else is instantiated for it, and the kernels that run with both off are untouched (profiles/body_wrench.txt).
 #if defined(__HIPCC__)
 constexpr bool kContactForceDefault = false;
 #else
@@ -2670,7 +2705,7 @@ SS_DEV bool run_env(W *w, const KArgs *k, const uint32_t *T, real *L, int env, i
   const ss_state &st = k->st;
   const bool fused_pass = mode != k->mode;                    // the in-launch reset of an env that just finished
   if (!fused_pass && k->mask && !k->mask[env]) return false;
-  Sim<W, DOFP, CANDP, SLOTP, NPASS, SHAPED, HT, SELFCOL, IMIT> sim;
+  Sim<W, DOFP, CANDP, SLOTP, NPASS, SHAPED, HT, SELFCOL, IMIT, BODYOUT && CFORCE> sim;
   sim.init(w, k, T, L, env, pool);
   int lane = sim.lane;
   real *qg = gptr(st.qpos) + (size_t)env * h.nq, *vg = gptr(st.qvel) + (size_t)env * h.nv;
@@ -2721,6 +2756,11 @@ SS_DEV bool run_env(W *w, const KArgs *k, const uint32_t *T, real *L, int env, i
     }
   }
 
+  // ss_set_body_wrench_input: the caller's own mj_steps only (k->xfrc is null in reset launches; `mode` is the parameter, so the fused
+  // reset pass of an env that just finished runs without it, as the reference's reset clears mjData first)
+  // An env that a bad state resets (reset_data) runs without it for the rest of the launch.
+  if constexpr (BODYOUT && CFORCE)
+    if (k->xfrc && mode != MODE_RESET) sim.set_wrench_ptr(k->xfrc + (size_t)env * (6 * h.nb));
   // ---- initial LDS state
   sim.load(sim.a, wg, h.nv);
   if (mode == MODE_RESET) {

@@ -50,6 +50,40 @@ class _MjDataView:
     def ctrl(self):
         return np.zeros(self._e._vec.nu)
 
+    @property
+    def xfrc_applied(self):
+        """mjData.xfrc_applied of env 0: a writable [nbody, 6] view (force at the centre of mass ; torque, world frame) of the batch's
+        wrench tensor, rows in the order of body_names_orig (no world body: MuJoCo's body id - 1).  Reading or writing it turns the
+        input on (SMPLSimVecEnv.enable_body_wrenches); the next step applies what it holds."""
+        return _XfrcView(self._e._vec.enable_body_wrenches()[0])
+
+    @xfrc_applied.setter
+    def xfrc_applied(self, value):
+        self.xfrc_applied[...] = value
+
+
+class _XfrcView:
+    """numpy-style indexing onto one env's [nbody, 6] rows of the device tensor: reads copy to the host, writes go to the device."""
+
+    def __init__(self, rows):
+        self._t = rows
+        self.shape, self.dtype = tuple(rows.shape), np.float64
+
+    def __array__(self, dtype=None, copy=None):
+        return self._t.cpu().numpy().astype(dtype or np.float64)
+
+    def __getitem__(self, idx):
+        return np.asarray(self)[idx]
+
+    def __setitem__(self, idx, value):
+        import torch
+        a = np.asarray(self)
+        a[idx] = value                                       # numpy's indexing and broadcasting rules
+        self._t.copy_(torch.as_tensor(a, dtype=torch.float32))
+
+    def __repr__(self):
+        return repr(np.asarray(self))
+
 
 class HumanoidEnv:
     metadata = {"render_modes": ["human", "rgb_array"], "render_fps": 30}

@@ -175,6 +175,15 @@ class SMPLSimImitationVecEnv:
         self.contact_force = self.base.enable_contact_forces()
         return self.contact_force
 
+    def enable_body_wrenches(self):
+        """SMPLSimVecEnv.enable_body_wrenches of the stepped batch: `xfrc_applied` [N, nbody, 6], applied by every following step,
+        fused or not; the re-initialisation of a finished env runs without it."""
+        self.xfrc_applied = self.base.enable_body_wrenches()
+        return self.xfrc_applied
+
+    def disable_body_wrenches(self):
+        self.base.disable_body_wrenches()
+
     def reference_actions(self):
         """PD targets that replay the clip: the next frame's joint angles in action units (dof_pos / pi, the reference's own
         replay recipe in examples/motion_lib_test.py:67) — a policy-free tracking baseline."""

@@ -115,6 +115,21 @@ class ShapeVariedVecEnv:
             self.qpos[a:b].copy_(env.qpos); self.qvel[a:b].copy_(env.qvel)
         return self.qpos, self.qvel
 
+    def enable_body_wrenches(self):
+        """SMPLSimVecEnv.enable_body_wrenches for all envs: `xfrc_applied` [N, nbody, 6], edited in place by the caller (shape
+        groups on streams: every group reads its rows of the one tensor)."""
+        if getattr(self, "xfrc_applied", None) is None:
+            self.xfrc_applied = torch.zeros(self.num_envs, self.nbody, 6, device=self.device)
+        starts = [0] if self.single is not None else self.starts
+        for env, a in zip(self.envs, starts):
+            env.xfrc_applied = self.xfrc_applied[a:a + env.num_envs]
+            env.enable_body_wrenches()
+        return self.xfrc_applied
+
+    def disable_body_wrenches(self):
+        for env in self.envs:
+            env.disable_body_wrenches()
+
     def close(self):
         for e in self.envs:
             e.close()
