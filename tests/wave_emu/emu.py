@@ -18,10 +18,12 @@ _LIBS = {}
 _LOCK = threading.Lock()              # parity_tools steps batches from a thread pool: one `make`, one load
 
 
-def lib(f64=False):
+def lib(f64=False, prof=False):
     """f64=True: the float64 instantiation of the same kernel source (-DSS_F64, Newton run to convergence): every array of
-    the C ABI declared float* is then a float64 array."""
-    name = "libss_emu64.so" if f64 else "libss_emu.so"
+    the C ABI declared float* is then a float64 array.  prof=True (float64 only): the same with the kernel's stage counters compiled
+    in (-DSS_PROFILE; EmuBatch.prof)."""
+    assert f64 or not prof
+    name = "libss_emu64_prof.so" if prof else "libss_emu64.so" if f64 else "libss_emu.so"
     with _LOCK:
         if name not in _LIBS:
             subprocess.check_call(["make", "-s", "-C", _HERE, name])
@@ -43,10 +45,10 @@ def _rand4(tr, n, ft=np.float32):
 
 
 class EmuBatch:
-    def __init__(self, mc, tables, num_envs, legal_bodies=(), timestep=1.0 / 450, shape_mcs=None, shape_id=None, f64=False, mjcf_text=None, mjcf_options=None, **cfg):
+    def __init__(self, mc, tables, num_envs, legal_bodies=(), timestep=1.0 / 450, shape_mcs=None, shape_id=None, f64=False, mjcf_text=None, mjcf_options=None, prof=False, **cfg):
         """shape_mcs: list of ModelConst = body shapes of one humanoid (ss_model_create_shapes), shape_id [N] picks per env.
         f64: run the float64 instantiation of the kernel (state / action / observation arrays are float64 then)."""
-        L = self.L = lib(f64)
+        L = self.L = lib(f64, prof)
         ft = self.ft = np.float64 if f64 else np.float32
         self.mc = mc
         self.model = C.c_void_p()
@@ -146,6 +148,12 @@ class EmuBatch:
         self.self_records = np.zeros((self.N, _cabi.SS_MAX_SELF_CONTACTS, 24), self.ft)
         self._chk(self.L.ss_debug_self_contacts(self.batch, _p(self.self_records)))
         return self.self_records
+
+    def prof(self, n=64):
+        """The kernel's counters (ss_kernel.h PF_*), summed over every launch of this batch so far (prof=True builds)."""
+        out = np.zeros(n, np.uint64)
+        self._chk(self.L.ss_debug_prof(self.batch, _p(out), n))
+        return out
 
     def debug_forward(self, torques=None):
         nv = self.mc.nv
